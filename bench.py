@@ -5,8 +5,9 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One STEP = one launch of the step kernel over one batch of the synthetic RPC replay: `--rounds`
-consecutive rounds x (one event per raft group), inputs and outputs resident in HBM; every step consumes
-FRESH rounds of the stream, so no step sees cached or replayed state.
+consecutive rounds x (one event per raft group), inputs and outputs resident in HBM; every step decides rows that are
+fresh for the table state it meets: the stream's next rounds, or — past --max-staged steps — a staged batch replayed after
+the initial state was reloaded (see below), never rows the table has already decided.
   N = 1   BASELINE config 3, the configuration the metric is quoted on: 65 536 groups x 5 peers on one GPU,
           ~20 % leader view / ~80 % follower view, 1 % higher-term events, elections keep the mix stationary
           (seed 0xC0FFEE02).
@@ -16,7 +17,12 @@ FRESH rounds of the stream, so no step sees cached or replayed state.
           way.  Embarrassingly parallel: no collective on the data path; three scalars (MAX elapsed,
           SUM decisions, SUM bytes) are added up on the host through gloo.  Per-GPU work is fixed: scaling is "weak".
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+At most --max-staged batches are staged (generated in blocks of groups by worker processes); a run of more steps goes round them, the initial
+state reloaded outside the timing whenever it starts again at the first one, so every launch still meets rows that are fresh for its state.
+--dump-outputs DIR writes what the last timed launch returned (float64 .npy files) so that two builds can be compared output for output.
+
+Prints ONE JSON line on rank 0. A plain run carries the headline (value, ms_per_step, the run's shape, the timed launches' counters) and
+nothing else; --full adds every other leg, among them two extra objects:
   roofline      HBM bytes the launch really moved (rocprofv3 PMC passes of this very command and library build,
                 profiles/traffic.json — a quotation, flagged as such) / average step-kernel launch duration, measured with
                 a HIP event pair on the table's stream around the K timed launches (inter-launch gaps included), against
@@ -38,6 +44,9 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+# the keys of a plain run's line (without --full): the headline, the run's shape and what the timed launches themselves counted
+PLAIN_KEYS = ("metric", "value", "unit", "n_gpus", "n_gpus_seen", "launcher", "per_gpu", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+              "dtype", "data", "config", "counters", "int64_body_workgroups", "stage_seconds", "staged_batches", "full")
 HBM_PEAK_GBPS = 8000.0      # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md)
 
 
@@ -77,7 +86,143 @@ def parse():
     ap.add_argument("--pmc-timeout", type=int, default=150, help="seconds one counter pass may take before it is abandoned (the quoted values stand in)")
     ap.add_argument("--wide-rows", action="store_true", help="stage the batches as rg_batch_t (40 B + 8n per row, 64-bit fields) and decide them with the "
                     "wide-row kernels instead of the default compact rows (rg_batch32_t, 24 B per row) / rg::step32_kernel")
+    ap.add_argument("--full", action="store_true", help="also run every leg beside the headline: the copy yardstick's figure, the per-launch spread, the counter passes, "
+                    "the check against the committed reference digests, the host-memory legs, the CPU baseline, the 64-bit-body pass, the adverse-mix, long-lived, "
+                    "long-launch and once-per-tick legs and the roofline block. Without it the run stages, warms up, times the steps and prints the headline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last timed step returned (its compact outcome rows "
+                    "and persist rows at a fixed, seeded sample of rows, and the table's state after it) as DIR/<name>.npy in float64")
+    ap.add_argument("--max-staged", type=int, default=64, help="at most this many distinct batches of the stream are staged in HBM; longer runs go round them, "
+                    "reloading the initial state (outside the timing) each time they start again at the first batch. 64 (10.7 GB of rows + outcome rows at "
+                    "config 3) stage in about 9 s with 15 workers on an MI355X host; each wrap costs ~5.5 ms of reload outside the timing and one restart of "
+                    "the launch queue inside it (measured: ~1 us per step at 64, ~4 us at 16), so fewer staged batches trade staging time for both")
+    ap.add_argument("--stage-workers", type=int, default=None, help="processes that generate the stream in blocks of groups (default: one fewer than the usable CPUs, at most 15, at N=1; 1 at N>1)")
     return ap.parse_args()
+
+
+def stage_worker_default():
+    """staging processes of a one-GPU run: one fewer than the CPUs this process may use (OMP_NUM_THREADS, where set, caps them), at most 15 — with the
+    bench process itself never more than 16 processes that load the HIP runtime"""
+    cpus = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    if omp.isdigit() and int(omp) > 0:
+        cpus = min(cpus, int(omp))
+    return max(1, min(15, cpus - 1))
+
+
+def _stage_worker(conn, cfg, first_gid, count, rounds, nb, followers):
+    """One block of groups of the stream, batch after batch, packed to compact rows: (head, abcd, decisions, algorithmic bytes) per batch down `conn`.
+    A group's stream depends on its global id only (rafting_amd/workload.py), so the blocks interleave into exactly the batches one generator makes."""
+    try:
+        from rafting_amd import engine, workload
+        gen = workload.ReplayGenerator(cfg, first_gid=first_gid, count=count)
+        for _ in range(nb):
+            b = gen.next_batch(rounds)
+            dec, alg = workload.batch_stats(b, followers)[:2]
+            b32 = engine.pack32(b)
+            conn.send(("ok", b32.head, b32.abcd, b32.entry_count, dec, alg))
+    except Exception as e:
+        conn.send(("error", "%s: %s" % (type(e).__name__, e)))
+    finally:
+        conn.close()
+
+
+def stage_compact(cfg, first_gid, count, rounds, nb, workers, followers):
+    """Yields (abi.Batch32, (decisions, algorithmic bytes)) for the next `nb` batches of the stream of groups [first_gid, first_gid + count): generated by `workers`
+    processes, each a block of the groups, interleaved round by round. The same rows a single ReplayGenerator + pack32 give (tests/test_bench_staging_cpu.py)."""
+    from rafting_amd import abi, engine, workload
+    workers = max(1, min(workers, count // 1024))
+    if workers == 1:
+        gen = workload.ReplayGenerator(cfg, first_gid=first_gid, count=count)
+        for _ in range(nb):
+            b = gen.next_batch(rounds)
+            yield engine.pack32(b), workload.batch_stats(b, followers)[:2]
+        return
+    import multiprocessing as mp
+    ctx = mp.get_context("spawn")                      # (never fork a process that holds the GPU: the workers start clean and only generate and pack)
+    bounds = [first_gid + count * w // workers for w in range(workers + 1)]
+    procs, conns = [], []
+    try:
+        for w in range(workers):
+            parent, child = ctx.Pipe(duplex=False)
+            p = ctx.Process(target=_stage_worker, args=(child, cfg, bounds[w], bounds[w + 1] - bounds[w], rounds, nb, followers), daemon=True)
+            p.start()
+            child.close()
+            procs.append(p)
+            conns.append(parent)
+        for _ in range(nb):
+            head = np.empty((rounds, count), dtype=abi.HEAD_DT)
+            abcd = np.empty((rounds, count), dtype=abi.QUAD32_DT)
+            dec = alg = 0
+            for w, conn in enumerate(conns):
+                msg = conn.recv()
+                if msg[0] != "ok":
+                    raise RuntimeError("bench: staging worker %d: %s" % (w, msg[1]))
+                _, h, q, n_terms, d, a = msg
+                if n_terms:                            # (entry terms of their own would need their offsets rebased: the stream's rows never carry any)
+                    raise RuntimeError("bench: staging worker %d: a row needs entry terms of its own" % w)
+                lo, hi = bounds[w] - first_gid, bounds[w + 1] - first_gid
+                head[:, lo:hi] = h.reshape(rounds, hi - lo)
+                abcd[:, lo:hi] = q.reshape(rounds, hi - lo)
+                dec, alg = dec + d, alg + a
+            yield abi.Batch32(rounds, count, None, head.reshape(-1), abcd.reshape(-1), np.zeros(1, dtype=np.int32), 0), (dec, alg)
+    finally:
+        for conn in conns:
+            conn.close()
+        for p in procs:
+            p.join(timeout=10)
+            if p.is_alive():
+                p.kill()
+
+
+DUMP_ROWS = 1 << 18          # outcome rows written by --dump-outputs: a fixed, seeded sample (all of them when there are fewer)
+DUMP_BYTES = 64 << 20        # all the files --dump-outputs writes, every rank's together
+
+
+def dump_outputs(directory, table, db, compact_out, world, rank):
+    """--dump-outputs: what the last timed launch returned to its caller — its outcome rows (compact rows: rg_out32_t, and the rg_persist32_t of the rows
+    flagged RG_F_PERSIST, 0 elsewhere; wide outcomes: rg_outcome_t's reply / log-effect / persist columns) at up to DUMP_ROWS rows drawn with a fixed seed — and
+    the table's state after it, every column, for every group or for groups drawn with a fixed seed where they would not fit; float64 .npy files (every value
+    is an integer below 2^53), prefixed rank<r>_ when there are several ranks, DUMP_BYTES in all"""
+    from rafting_amd import abi
+    os.makedirs(directory, exist_ok=True)
+    pre = "rank%d_" % rank if world > 1 else ""
+    budget = DUMP_BYTES // world
+    st = table.read_state()
+    G, F = table.groups, table.cluster - 1
+    per_group = sum(getattr(st, f).size for f in st.fields()) / G + 1           # values per group (runs and peer records included) and its index
+    n_rows = min(db.rows, DUMP_ROWS, budget // 2 // (9 * 8))                    # rows: the index, four outcome and four persist values
+    n_groups = min(G, int((0.97 * budget - n_rows * 9 * 8) // (8 * per_group)))     # (3 % of the budget spare: the drawn groups may hold more runs than the mean)
+    rng = np.random.default_rng(0x5EED)
+    rows = np.arange(db.rows) if n_rows == db.rows else np.sort(rng.choice(db.rows, n_rows, replace=False))
+    groups = np.arange(G) if n_groups >= G else np.sort(rng.choice(G, n_groups, replace=False))
+    arrays = {"rows": rows, "groups": groups}
+    if compact_out:
+        o = db.outcome32()
+        for f in abi.OUT32_DT.names:
+            arrays["out_" + f] = o.row[f][rows]
+        persisted = (o.row["flags"][rows] & abi.F_PERSIST) != 0
+        for f in abi.PERSIST32_DT.names:
+            arrays["persist_" + f] = np.where(persisted, o.persist[f][rows], 0)
+    else:
+        o = db.outcome()
+        flags = o.reply["flags"][rows]
+        valid = {"reply": np.ones(len(rows), dtype=bool), "logfx": (flags & (abi.F_COMMIT | abi.F_LOG_APPEND | abi.F_LOG_TRUNC)) != 0,
+                 "persist": (flags & abi.F_PERSIST) != 0}     # (the log-effect and persist rows are written where the reply flags them only)
+        for col in ("reply", "logfx", "persist"):
+            a = getattr(o, col)[rows]
+            for f in a.dtype.names:
+                arrays["%s_%s" % (col, f)] = np.where(valid[col], a[f], 0)
+    # the state of the drawn groups: per-group columns, the F peer records of each (group-major), and each group's term runs (run_offset / run_count)
+    runs = np.concatenate([np.arange(st.run_offset[g], st.run_offset[g] + st.run_count[g], dtype=np.int64) for g in groups]) if len(groups) < G else None
+    for f in st.fields():
+        a = getattr(st, f)
+        if len(groups) < G:
+            a = a[runs] if f in ("run_start", "run_term") else (a.reshape(G, F)[groups].reshape(-1) if f.startswith("peer_") else a[groups])
+        arrays["state_" + f] = a
+    total = sum(np.asarray(a).size * 8 for a in arrays.values())
+    assert total <= budget, "bench: --dump-outputs would write %d bytes, more than its %d" % (total, budget)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, pre + name + ".npy"), np.asarray(a).astype(np.float64))
 
 
 def self_launch(n):
@@ -134,12 +279,12 @@ def pmc_passes(args, argv):
         if skip_next:
             skip_next = False
             continue
-        if a in ("--steps", "--warmup", "--cpu-batches", "--pcie-batches", "--adverse-batches", "--index-base-batches", "--tick-batches", "--pmc-timeout", "--copy-bytes", "--long-launch-rounds",
+        if a in ("--steps", "--warmup", "--dump-outputs", "--cpu-batches", "--pcie-batches", "--adverse-batches", "--index-base-batches", "--tick-batches", "--pmc-timeout", "--copy-bytes", "--long-launch-rounds",
                  "--long-launch-batches"):
             skip_next = True
             continue
-        if a.split("=")[0] in ("--steps", "--warmup", "--tick-batches", "--index-base-batches", "--long-launch-rounds", "--long-launch-batches") or a in ("--no-cpu-baseline", "--no-pcie", "--no-int64-pass", "--no-adverse",
-                                                                                                       "--no-copy-bw", "--copy-bw", "--no-pmc"):
+        if a.split("=")[0] in ("--steps", "--warmup", "--dump-outputs", "--tick-batches", "--index-base-batches", "--long-launch-rounds", "--long-launch-batches") or a in ("--no-cpu-baseline", "--no-pcie", "--no-int64-pass", "--no-adverse",
+                                                                                                       "--no-copy-bw", "--copy-bw", "--no-pmc", "--full"):
             continue
         keep.append(a)
     child = [sys.executable, os.path.abspath(__file__)] + keep + ["--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--no-pcie", "--no-int64-pass", "--no-adverse",
@@ -241,18 +386,53 @@ def main():
     st0 = gen.initial_state()
     table.load_state(st0)
 
-    # ---- stage (warmup + steps) fresh batches of the stream in HBM -------------------------------
+    # ---- stage (warmup + steps) fresh batches of the stream in HBM, at most --max-staged of them -------------------------------
+    # A run of more steps goes round the staged batches: each time it starts again at the first one, the table's initial state is reloaded first (outside the
+    # timing), so every step decides rows that are fresh for the state it meets — the same launches, in the same order, as the stream's first batches.
     t_gen = time.time()
-    nb = args.warmup + args.steps
+    nb = min(args.warmup + args.steps, max(args.max_staged, 1))
     dbatches, stats, keep_host = [], [], []
     compact_out = not args.wide_rows and not args.wide_outcomes
-    for i in range(nb):
-        b = gen.next_batch(args.rounds)
-        stats.append(workload.batch_stats(b, F)[:2])
-        dbatches.append(engine.DeviceBatch(table, b) if args.wide_rows else engine.DeviceBatch32(table, b, compact=compact_out, wide=False))
-        if rank == 0 and world == 1 and not args.no_cpu_baseline and i < args.cpu_batches:
-            keep_host.append(b)
+    if args.wide_rows:
+        for i in range(nb):
+            b = gen.next_batch(args.rounds)
+            stats.append(workload.batch_stats(b, F)[:2])
+            dbatches.append(engine.DeviceBatch(table, b))
+    else:
+        workers = args.stage_workers if args.stage_workers is not None else (stage_worker_default() if world == 1 else 1)
+        for b32, s in stage_compact(cfg, first_gid, count, args.rounds, nb, workers, F):
+            stats.append(s)
+            dbatches.append(engine.DeviceBatch32(table, b32, compact=compact_out, wide=False))
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
+        hgen = workload.ReplayGenerator(cfg, first_gid=first_gid, count=count)      # (the stream again, from its first round: the CPU baseline's host batches)
+        keep_host = [hgen.next_batch(args.rounds) for _ in range(min(args.cpu_batches, nb))]
     t_gen = time.time() - t_gen
+
+    def run_steps(tbl, start, n, timed):
+        """n launches on `tbl` from position `start` of the stream (staged batch start % nb); the initial state is reloaded where a launch starts the staged
+        batches again. timed: -> (wall seconds, HIP-event ms) summed over the stretches between reloads, the reloads themselves outside both"""
+        wall = ev = 0.0
+        pos, end = start, start + n
+        while pos < end:
+            if pos % nb == 0 and pos > 0:
+                tbl.load_state(st0)
+            stop = min(end, (pos // nb + 1) * nb)
+            last = stop == end
+            if timed:
+                if pos == start:
+                    barrier()
+                t0 = time.perf_counter()
+                tbl.timing_begin()                 # one HIP event pair on the table's stream around the launches
+            for i in range(pos, stop):
+                tbl.submit_device(dbatches[i % nb])
+            if timed:
+                ev += tbl.timing_end()             # records the stop event and waits for it
+                tbl.sync()
+                if last:
+                    barrier()
+                wall += time.perf_counter() - t0
+            pos = stop
+        return wall, ev
 
     def outcomes_of(k):
         """the wide image of the first k launches' outcome rows; compact outcome rows carry the role epoch only where it changes (rg_persist32_t),
@@ -270,11 +450,11 @@ def main():
     # which the device sits idle, and the launches right after an idle spell run slow — measured on one box, alternating runs, the yardstick after the timed
     # region against before the warm-up: kernel 0.0623 -> 0.0615 ms, ms_per_step 0.0686 - 0.0707 -> 0.0655 - 0.0658 at 10 steps, 0.0649 - 0.0654 -> 0.0630 - 0.0636 at 20
     # (profiles/r07a_copy_first_ab.jsonl; RG_BENCH_COPY_LAST=1 restores the old order). The timed region itself is what it was: K fresh steps, all of them timed.
+    # Without --full the copy still runs here, as the device's warm-up after the staging; only --full reports its figure.
     copy_gbps_early = None
     if os.environ.get("RG_BENCH_COPY_LAST") != "1" and not args.no_copy_bw:
         copy_gbps_early = table.copy_bandwidth(args.copy_bytes, int(os.environ.get("RG_BENCH_COPY_ITERS", "10")))
-    for i in range(args.warmup):
-        table.submit_device(dbatches[i])
+    run_steps(table, 0, args.warmup, timed=False)
     table.sync()
     table.counters(reset=True)
     if not args.wide_rows:
@@ -282,24 +462,20 @@ def main():
             table.wide_body_workgroups(reset=True)
         except engine.EngineError:
             pass
-    barrier()
-    t0 = time.perf_counter()
-    table.timing_begin()                 # one HIP event pair on the table's stream around the K launches
-    for i in range(args.warmup, nb):
-        table.submit_device(dbatches[i])
-    kernel_ms = table.timing_end()       # records the stop event and waits for it
-    table.sync()
-    barrier()
-    elapsed = time.perf_counter() - t0
+    elapsed, kernel_ms = run_steps(table, args.warmup, args.steps, timed=True)
     launches = args.steps
+    last_batch = dbatches[(args.warmup + args.steps - 1) % nb]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, table, last_batch, compact_out, world, rank)
     counters = table.counters()
     try:
         wide_wgs = None if args.wide_rows else table.wide_body_workgroups()   # workgroups of the timed launches that left the 32-bit domain (0 on this stream)
     except engine.EngineError:                                                # (an experiment build of an older tree: RG_LIB)
         wide_wgs = None
 
-    decisions = sum(s[0] for s in stats[args.warmup:])
-    alg_bytes = sum(s[1] for s in stats[args.warmup:])
+    timed_stats = [stats[i % nb] for i in range(args.warmup, args.warmup + args.steps)]
+    decisions = sum(s[0] for s in timed_stats)
+    alg_bytes = sum(s[1] for s in timed_stats)
     elapsed_rank = elapsed
     elapsed, (decisions_all, alg_all) = shard.aggregate(elapsed, [decisions, alg_bytes], device=red_dev if world > 1 else None)
     per_gpu = shard.gather_rows([decisions / elapsed_rank, elapsed_rank / args.steps * 1e3, kernel_ms / max(launches, 1), float(dev)],
@@ -308,7 +484,7 @@ def main():
     # the measured-copy yardstick, same run, same device (taken in front of the warm-up unless RG_BENCH_COPY_LAST=1)
     if copy_gbps_early is not None:
         copy_gbps = copy_gbps_early
-    elif args.no_copy_bw:
+    elif args.no_copy_bw or not args.full:
         copy_gbps = None
     else:
         copy_gbps = table.copy_bandwidth(args.copy_bytes, 10)
@@ -317,7 +493,7 @@ def main():
     # launch decides what it decided in the timed region and leaves the same outcome rows — each bracketed by its own HIP event pair on the table's stream
     # (the device is idle between them: a launch's own duration, without the inter-launch gaps the region figure includes). Reported, never `value`.
     spread = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             table.load_state(st0)
             each = []
@@ -325,7 +501,9 @@ def main():
                 table.timing_begin()
                 table.submit_device(dbatches[i])
                 each.append(table.timing_end())
-            timed_each = np.sort(np.asarray(each[args.warmup:]))
+            # (the staged batches the timed steps used: with --warmup at or past --max-staged the timed steps start again at the first batch)
+            used = sorted({i % nb for i in range(args.warmup, args.warmup + min(args.steps, nb))})
+            timed_each = np.sort(np.asarray([each[i] for i in used]))
             spread = {"launches": int(len(timed_each)), "min_ms": float(timed_each[0]), "median_ms": float(timed_each[len(timed_each) // 2]),
                       "max_ms": float(timed_each[-1]), "mean_ms": float(timed_each.mean()),
                       "note": "one HIP event pair per launch, device idle in between; the same launches as the timed region (state reloaded, same batches)"}
@@ -340,7 +518,7 @@ def main():
     # is not on PATH, under --no-pmc, inside such a child, on more than one rank, or when a pass fails or runs out of time.
     pmc = None
     under_profiler = any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ) or "rocprofiler" in os.environ.get("LD_PRELOAD", "")      # (no profiler inside a profiler)
-    if rank == 0 and world == 1 and not args.no_pmc and not args.wide_rows and not os.environ.get("RG_BENCH_UNDER_PMC") and not os.environ.get("RG_ALLOW_HOST_EMULATION") \
+    if args.full and rank == 0 and world == 1 and not args.no_pmc and not args.wide_rows and not os.environ.get("RG_BENCH_UNDER_PMC") and not os.environ.get("RG_ALLOW_HOST_EMULATION") \
             and not under_profiler:
         pmc = pmc_passes(args, sys.argv[1:])
 
@@ -363,41 +541,42 @@ def main():
                     and (("shard" in c) == (cfg.groups != gpg)):
                 return name, c
         return None, None
-    try:
-        from tools import make_golden
-        first_out = outcomes_of(1)[0]
-        case_name, c = case_of(first_gid // gpg)
-        if c is not None:
-            verdict = 1.0 if make_golden.canonical_outcome_digest(first_out) == c["outcomes"] else 0.0
-    except Exception as e:      # a reporting leg must not take the bench line down with it
-        print("bench: golden leg failed on rank %d: %r" % (rank, e), file=sys.stderr)
-    verdicts = shard.gather_rows([verdict, float(first_gid // gpg)], device=red_dev if world > 1 else None)
-    if rank == 0:
+    if args.full:                                       # (the check against the committed digest is a --full leg)
         try:
-            names = {0.0: "MISMATCH", 1.0: "ok", -1.0: "no committed case"}
-            if world == 1:
-                golden = None if case_name is None else {"case": case_name, "outcomes": names[verdict]}
-            else:
-                golden = [{"rank": r, "case": case_of(int(row[1]))[0] if row[0] >= 0 else None, "outcomes": names[float(row[0])]} for r, row in enumerate(verdicts)]
-            # layout floor: event rows in (8 + 16 B, or 40 B + entry terms on wide rows), reply rows out (16 B), the log / commit and persist rows that
-            # exist (16 B each, counted on the stream's first launch), the table once per launch (5 + 4 columns of 16 B in, 5 out, run columns
-            # and the follower records of leading groups when dirty: bounded here by "all of them")
-            f0 = first_out.reply["flags"]
-            rows0 = len(f0)
-            lfx_rows = int(np.count_nonzero((f0 & (abi.F_COMMIT | abi.F_LOG_APPEND | abi.F_LOG_TRUNC)) != 0))
-            per_rows = int(np.count_nonzero((f0 & abi.F_PERSIST) != 0))
-            ev_bytes = dbatches[0].bytes_in if hasattr(dbatches[0], "bytes_in") else rows0 * 40
-            state_bytes = gpg * (9 * 16 + 5 * 16 + 4 * 16) + int(gpg * cfg.leader_frac) * F * 32 * 2
-            # (an ESTIMATE of what this row / table layout moves, from the first launch's row counts and every table column once — not a lower bound:
-            # ADVICE r4. With compact outcome rows every event has one 16-byte row and only the persist rows are conditional.)
-            floor_bytes = ev_bytes + rows0 * 16 + ((per_rows if compact_out else lfx_rows + per_rows) * 16) + state_bytes
+            from tools import make_golden
+            first_out = outcomes_of(1)[0]
+            case_name, c = case_of(first_gid // gpg)
+            if c is not None:
+                verdict = 1.0 if make_golden.canonical_outcome_digest(first_out) == c["outcomes"] else 0.0
         except Exception as e:      # a reporting leg must not take the bench line down with it
-            print("bench: layout-estimate leg failed: %r" % (e,), file=sys.stderr)
-    if world > 1 or rank == 0:
-        if any(float(row[0]) == 0.0 for row in verdicts):
-            if rank == 0:
-                print("bench: a rank's first launch does not reproduce the reference's digest: %r" % ([list(map(float, r)) for r in verdicts],), file=sys.stderr)
-            sys.exit(3)
+            print("bench: golden leg failed on rank %d: %r" % (rank, e), file=sys.stderr)
+        verdicts = shard.gather_rows([verdict, float(first_gid // gpg)], device=red_dev if world > 1 else None)
+        if rank == 0:
+            try:
+                names = {0.0: "MISMATCH", 1.0: "ok", -1.0: "no committed case"}
+                if world == 1:
+                    golden = None if case_name is None else {"case": case_name, "outcomes": names[verdict]}
+                else:
+                    golden = [{"rank": r, "case": case_of(int(row[1]))[0] if row[0] >= 0 else None, "outcomes": names[float(row[0])]} for r, row in enumerate(verdicts)]
+                # layout floor: event rows in (8 + 16 B, or 40 B + entry terms on wide rows), reply rows out (16 B), the log / commit and persist rows that
+                # exist (16 B each, counted on the stream's first launch), the table once per launch (5 + 4 columns of 16 B in, 5 out, run columns
+                # and the follower records of leading groups when dirty: bounded here by "all of them")
+                f0 = first_out.reply["flags"]
+                rows0 = len(f0)
+                lfx_rows = int(np.count_nonzero((f0 & (abi.F_COMMIT | abi.F_LOG_APPEND | abi.F_LOG_TRUNC)) != 0))
+                per_rows = int(np.count_nonzero((f0 & abi.F_PERSIST) != 0))
+                ev_bytes = dbatches[0].bytes_in if hasattr(dbatches[0], "bytes_in") else rows0 * 40
+                state_bytes = gpg * (9 * 16 + 5 * 16 + 4 * 16) + int(gpg * cfg.leader_frac) * F * 32 * 2
+                # (an ESTIMATE of what this row / table layout moves, from the first launch's row counts and every table column once — not a lower bound:
+                # ADVICE r4. With compact outcome rows every event has one 16-byte row and only the persist rows are conditional.)
+                floor_bytes = ev_bytes + rows0 * 16 + ((per_rows if compact_out else lfx_rows + per_rows) * 16) + state_bytes
+            except Exception as e:      # a reporting leg must not take the bench line down with it
+                print("bench: layout-estimate leg failed: %r" % (e,), file=sys.stderr)
+        if world > 1 or rank == 0:
+            if any(float(row[0]) == 0.0 for row in verdicts):
+                if rank == 0:
+                    print("bench: a rank's first launch does not reproduce the reference's digest: %r" % ([list(map(float, r)) for r in verdicts],), file=sys.stderr)
+                sys.exit(3)
 
     # ---- the same step with caller-owned HOST buffers (PCIe both ways): reported, never `value` -----------------------------
     # Three ways over the link, each from the same table state with the same FRESH batches of the stream (B0, B1 size the staging
@@ -406,7 +585,7 @@ def main():
     # pipeline with int32 event fields up and packed logfx / persist lists down. The packed replies must equal the wide ones.
     pcie = pcie_pipe = pcie_packed = pcie_gbps = packed_gbps = None
     pcie_bytes = {}
-    if rank == 0 and world == 1 and not args.no_pcie:
+    if args.full and rank == 0 and world == 1 and not args.no_pcie:
         nb_h, n_size = args.pcie_batches, 2
         gen_p = workload.ReplayGenerator(cfg, first_gid=first_gid, count=count)      # the stream again, from its first round
         st_p = st0
@@ -535,7 +714,7 @@ def main():
     # workgroup has left the 32-bit tier's domain (>= 2^30). Same batches, a second table from the same initial state; its decision counters must
     # equal the first pass's (the outcome rows are bit-identical: tests/test_gpu_parity.py::test_compact_multi_round_launch_and_domain_exits).
     int64_pass = None
-    if rank == 0 and world == 1 and not args.wide_rows and not args.no_int64_pass:
+    if args.full and rank == 0 and world == 1 and not args.wide_rows and not args.no_int64_pass:
         os.environ["RG_FORCE_WIDE"] = "1"
         try:
             t2 = engine.Table(gpg, cfg.cluster, cfg.self_slot, cfg.pre_vote, device=dev)
@@ -544,15 +723,10 @@ def main():
         t2.load_state(st0)
         if not args.no_copy_bw:
             t2.copy_bandwidth(args.copy_bytes, 10)          # (the CPU baseline sits in front of this pass: the device out of its idle state first, as in front of the main leg)
-        for i in range(args.warmup):
-            t2.submit_device(dbatches[i])
+        run_steps(t2, 0, args.warmup, timed=False)
         t2.sync()
         t2.counters(reset=True)
-        t2.timing_begin()
-        for i in range(args.warmup, nb):
-            t2.submit_device(dbatches[i])
-        ms2 = t2.timing_end()
-        t2.sync()
+        ms2 = run_steps(t2, args.warmup, args.steps, timed=True)[1]
         c2 = t2.counters()
         int64_pass = {"ms": ms2 / max(args.steps, 1), "value": decisions / (ms2 * 1e-3) if ms2 > 0 else None,
                       "counters_equal_first_pass": [int(x) for x in c2] == [int(x) for x in counters]}
@@ -563,7 +737,7 @@ def main():
     # reply fan-in they start), and 1 % of the follower rows reach below the cached term runs (RG_NEED_HOST; the host parks the group for the rest of
     # the launch, which is what RG_SKIPPED_AFTER_NEED_HOST would do to its rows). `value_adverse_mix` counts APPLIED decisions only.
     adverse = None
-    if rank == 0 and world == 1 and not args.no_adverse and not args.wide_rows and not args.override and args.adverse_batches > 2:
+    if args.full and rank == 0 and world == 1 and not args.no_adverse and not args.wide_rows and not args.override and args.adverse_batches > 2:
         try:
             import dataclasses
             acfg = dataclasses.replace(cfg, name=cfg.name + " [adverse mix]", p_conflict=0.005, p_higher_term=max(cfg.p_higher_term, 0.01), p_miss=0.01,
@@ -613,7 +787,7 @@ def main():
     # table's index bases at 2^40 - 1, rows packed relative to them (rg_batch32_pack_rel). The 32-bit body must carry it at the headline's speed: no
     # workgroup on the 64-bit body. The first launch is checked against the oracle, which works on the absolute values.
     long_lived = None
-    if rank == 0 and world == 1 and args.index_base_batches > 2 and not args.wide_rows and not args.override:
+    if args.full and rank == 0 and world == 1 and args.index_base_batches > 2 and not args.wide_rows and not args.override:
         try:
             import dataclasses
             OFF = 1 << 40
@@ -670,7 +844,7 @@ def main():
     # ---- the same configuration handed over in LARGER batches: `--long-launch-rounds` rounds per launch instead of `--rounds`. A launch costs 7.5 us whatever its length and ends
     # with its slowest workgroup (DESIGN.md sections 6, 9); a host that can hand over more rounds at once pays both less often. Reported beside `value`, never as it.
     long_launch = None
-    if rank == 0 and world == 1 and args.long_launch_rounds > 0 and args.long_launch_batches > 1 and not args.wide_rows and not args.override:
+    if args.full and rank == 0 and world == 1 and args.long_launch_rounds > 0 and args.long_launch_batches > 1 and not args.wide_rows and not args.override:
         try:
             ggen = workload.ReplayGenerator(cfg, first_gid=first_gid, count=count)
             t5 = engine.Table(gpg, cfg.cluster, cfg.self_slot, cfg.pre_vote, device=dev)
@@ -707,7 +881,7 @@ def main():
     # Two ways: rg_submit_async_packed (nine runtime calls per tick) and rg_tick_launch (the same chain recorded once as a HIP graph, one call per tick);
     # plus what one single-round launch costs on the device when the rows already lie in HBM. A latency figure, never `value`.
     tick = None
-    if rank == 0 and world == 1 and args.tick_batches > 10 and not args.wide_rows and not args.override:
+    if args.full and rank == 0 and world == 1 and args.tick_batches > 10 and not args.wide_rows and not args.override:
         try:
             import gc
 
@@ -841,30 +1015,31 @@ def main():
         avg_kernel_s = kernel_ms * 1e-3 / max(launches, 1)
         # the vector-ALU side: instructions the launch issues against what the SIMDs can issue (one wave64 instruction per SIMD per four cycles)
         valu = None
-        try:
-            props = torch.cuda.get_device_properties(dev)
-            simds = int(props.multi_processor_count) * 4
-            clock_hz = float(getattr(props, "clock_rate", 2400000)) * 1e3
-            quoted = None
-            try:                                     # (the evidence pass's figure for this very library and workload, where there is one: profiles/valu.json)
-                for tr in json.load(open(os.path.join(ROOT, "profiles", "valu.json")))["entries"]:
-                    if (tr["config"], tr["groups_per_gpu"], tr["rounds"], tr["kernel"]) == (args.config, gpg, args.rounds, "%s<%d,false>" % ("rg::step32_kernel", F)) \
-                            and not args.override and tr.get("lib_sha16") == engine.library_sha16() and tr.get("outcome_format", "rg_outcome_t") == ("rg_outcome32_t" if compact_out else "rg_outcome_t"):
-                        quoted = tr
-            except (OSError, KeyError, ValueError):
-                pass
-            insts = pmc["SQ_INSTS_VALU"] if pmc and "SQ_INSTS_VALU" in pmc else (quoted["sq_insts_valu_per_launch"] if quoted else None)
-            if insts is not None and avg_kernel_s > 0:
-                peak = simds * clock_hz / 4.0
-                valu = {"insts_per_launch": insts, "per_64_groups_per_round": insts / max(1, (gpg + 63) // 64) / args.rounds,
-                        "achieved_ginst_per_s": insts / avg_kernel_s / 1e9, "peak_ginst_per_s": peak / 1e9, "busy_frac": insts / avg_kernel_s / peak,
-                        "simds": simds, "clock_mhz": clock_hz / 1e6, "peak_basis": "one wave64 vector instruction per SIMD per 4 cycles at the device's maximum clock",
-                        "salu_per_launch": pmc.get("SQ_INSTS_SALU") if pmc else (quoted or {}).get("sq_insts_salu_per_launch"),
-                        "lds_per_launch": pmc.get("SQ_INSTS_LDS") if pmc else (quoted or {}).get("sq_insts_lds_per_launch"),
-                        "measured_in_this_run": bool(pmc and "SQ_INSTS_VALU" in pmc), "lib_sha16": engine.library_sha16(),
-                        "source": "this run: rocprofv3 --pmc SQ_INSTS_VALU" if pmc and "SQ_INSTS_VALU" in pmc else quoted.get("source")}
-        except Exception as e:      # a reporting leg must not take the bench line down with it
-            print("bench: valu block failed: %r" % (e,), file=sys.stderr)
+        if args.full:
+            try:
+                props = torch.cuda.get_device_properties(dev)
+                simds = int(props.multi_processor_count) * 4
+                clock_hz = float(getattr(props, "clock_rate", 2400000)) * 1e3
+                quoted = None
+                try:                                     # (the evidence pass's figure for this very library and workload, where there is one: profiles/valu.json)
+                    for tr in json.load(open(os.path.join(ROOT, "profiles", "valu.json")))["entries"]:
+                        if (tr["config"], tr["groups_per_gpu"], tr["rounds"], tr["kernel"]) == (args.config, gpg, args.rounds, "%s<%d,false>" % ("rg::step32_kernel", F)) \
+                                and not args.override and tr.get("lib_sha16") == engine.library_sha16() and tr.get("outcome_format", "rg_outcome_t") == ("rg_outcome32_t" if compact_out else "rg_outcome_t"):
+                            quoted = tr
+                except (OSError, KeyError, ValueError):
+                    pass
+                insts = pmc["SQ_INSTS_VALU"] if pmc and "SQ_INSTS_VALU" in pmc else (quoted["sq_insts_valu_per_launch"] if quoted else None)
+                if insts is not None and avg_kernel_s > 0:
+                    peak = simds * clock_hz / 4.0
+                    valu = {"insts_per_launch": insts, "per_64_groups_per_round": insts / max(1, (gpg + 63) // 64) / args.rounds,
+                            "achieved_ginst_per_s": insts / avg_kernel_s / 1e9, "peak_ginst_per_s": peak / 1e9, "busy_frac": insts / avg_kernel_s / peak,
+                            "simds": simds, "clock_mhz": clock_hz / 1e6, "peak_basis": "one wave64 vector instruction per SIMD per 4 cycles at the device's maximum clock",
+                            "salu_per_launch": pmc.get("SQ_INSTS_SALU") if pmc else (quoted or {}).get("sq_insts_salu_per_launch"),
+                            "lds_per_launch": pmc.get("SQ_INSTS_LDS") if pmc else (quoted or {}).get("sq_insts_lds_per_launch"),
+                            "measured_in_this_run": bool(pmc and "SQ_INSTS_VALU" in pmc), "lib_sha16": engine.library_sha16(),
+                            "source": "this run: rocprofv3 --pmc SQ_INSTS_VALU" if pmc and "SQ_INSTS_VALU" in pmc else quoted.get("source")}
+            except Exception as e:      # a reporting leg must not take the bench line down with it
+                print("bench: valu block failed: %r" % (e,), file=sys.stderr)
         alg_per_launch = alg_bytes / max(args.steps, 1)
         achieved = alg_per_launch / avg_kernel_s / 1e9 if avg_kernel_s > 0 else 0.0
         moved_bytes = traffic * 1e9 if traffic is not None else floor_bytes
@@ -892,7 +1067,8 @@ def main():
                 "groups_per_gpu": gpg, "groups_total": gpg * world, "peers": cfg.cluster,
                 "rounds_per_step": args.rounds, "decisions_per_step_per_gpu": decisions // max(args.steps, 1),
                 "parallelism": "groups block-partitioned over %d GPU(s), no RCCL on the data path" % world,
-                "inputs": "HBM-resident event/outcome buffers (RG_MEM_DEVICE); every step consumes fresh rounds",
+                "inputs": "HBM-resident event/outcome buffers (RG_MEM_DEVICE); every step decides rows fresh for the state it meets (%d staged batches%s)" % (
+                    nb, "" if args.warmup + args.steps <= nb else ", replayed after a reload of the initial state each time the run starts again at the first"),
                 "rows": "rg_batch_t (wide: 8 + 16 + 16 B per row + 8 B per entry term)" if args.wide_rows else
                         "rg_batch32_t (compact: 8 + 16 B per row, the term shared by a row's entries in the row)",
                 "outcomes": "rg_outcome32_t (ABI 4, rg_submit32c: one 16 B row per event + a 16 B persist row per conversion)" if compact_out else
@@ -962,7 +1138,11 @@ def main():
             "counters": dict(zip(["rows", "replied", "role_conversions", "commit_advances", "asserts", "need_host",
                                   "dropped_stale", "log_appends"], counters)),
             "stage_seconds": t_gen,
+            "staged_batches": nb,
+            "full": bool(args.full),
         }
+        if not args.full:          # a plain run reports the headline and what the timed steps themselves gave; every other figure is a --full leg
+            out = {k: v for k, v in out.items() if k in PLAIN_KEYS}
         print(json.dumps(out), flush=True)
 
     for db in dbatches:

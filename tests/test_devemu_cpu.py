@@ -42,7 +42,7 @@ def test_bench_contract_end_to_end_on_the_emulation(emulation_library):
     import json
     env = dict(os.environ, RG_LIB=emulation_library, RG_SPLIT="1", RG_EMU_WAVES="1", RG_ALLOW_HOST_EMULATION="1", PYTHONPATH=ROOT)   # wavefront mode: bench.py's
     env.pop("RG_FAST", None)                                                    # default path is the two-wavefront compact-format kernel
-    p = subprocess.run([sys.executable, os.path.join(EMU, "bench_dry.py")], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+    p = subprocess.run([sys.executable, os.path.join(EMU, "bench_dry.py"), "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -93,7 +93,7 @@ def test_bench_with_two_ranks_is_config4_sharded_over_gloo(emulation_library):
     env = dict(os.environ, RG_LIB=emulation_library, RG_SPLIT="1", RG_EMU_WAVES="1", RG_ALLOW_HOST_EMULATION="1", PYTHONPATH=ROOT, OMP_NUM_THREADS="1")
     env.pop("RG_FAST", None)
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", str(port), os.path.join(EMU, "bench_dry.py"), "--gpus", "2", "--device", "0"],
+                        "--master-port", str(port), os.path.join(EMU, "bench_dry.py"), "--gpus", "2", "--device", "0", "--full"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -119,7 +119,7 @@ def test_a_rank_whose_first_launch_misses_the_reference_digest_fails_the_run(emu
     env = dict(os.environ, RG_LIB=emulation_library, RG_SPLIT="1", RG_EMU_WAVES="1", RG_ALLOW_HOST_EMULATION="1", PYTHONPATH=ROOT, OMP_NUM_THREADS="1",
                RG_GOLDEN_FILE=str(bad), RG_BENCH_ENTRY=os.path.join(EMU, "bench_dry.py"))
     env.pop("RG_FAST", None)
-    p = subprocess.run([sys.executable, os.path.join(EMU, "bench_dry.py"), "--gpus", "2", "--device", "0"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+    p = subprocess.run([sys.executable, os.path.join(EMU, "bench_dry.py"), "--gpus", "2", "--device", "0", "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode != 0
     assert not [ln for ln in p.stdout.splitlines() if ln.startswith("{")], p.stdout[-1000:]
     assert "does not reproduce the reference's digest" in p.stderr
@@ -134,7 +134,7 @@ def test_bench_starts_its_own_ranks_when_no_launcher_does(emulation_library):
                RG_BENCH_ENTRY=os.path.join(EMU, "bench_dry.py"))
     for k in ("RG_FAST", "WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(EMU, "bench_dry.py"), "--gpus", "2", "--device", "0"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+    p = subprocess.run([sys.executable, os.path.join(EMU, "bench_dry.py"), "--gpus", "2", "--device", "0", "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]
@@ -258,3 +258,56 @@ def test_multi_device_manager_is_race_free_under_thread_sanitizer(emulation_libr
     p = subprocess.run([exe, "48", "3", "40"], env=dict(os.environ, RG_SPLIT="0"), capture_output=True, text=True, timeout=900)
     assert p.returncode == 0 and "multi-device ok=1" in p.stdout, p.stdout + p.stderr[-3000:]
     assert "ThreadSanitizer" not in p.stderr, p.stderr[-3000:]
+
+
+def test_plain_bench_run_goes_round_the_staged_batches_and_dumps_the_last_step(emulation_library, tmp_path):
+    """bench.py without --full: the headline keys only, exactly --steps timed steps; with more steps than --max-staged the run goes round the staged
+    batches (initial state reloaded: no stale row, no assert), and --dump-outputs writes the last step's outputs, float64, the same in two runs"""
+    import json
+    import numpy as np
+    env = dict(os.environ, RG_LIB=emulation_library, RG_SPLIT="1", RG_EMU_WAVES="1", RG_ALLOW_HOST_EMULATION="1", PYTHONPATH=ROOT)
+    env.pop("RG_FAST", None)
+    lines, dumps = [], []
+    for k in range(2):
+        d = tmp_path / ("dump%d" % k)
+        p = subprocess.run([sys.executable, os.path.join(EMU, "bench_dry.py"), "--steps", "5", "--warmup", "1", "--max-staged", "3", "--dump-outputs", str(d)],
+                           cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+        assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
+        out = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(out) == 1
+        lines.append(json.loads(out[0]))
+        dumps.append(d)
+    r = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in r, k
+    assert r["full"] is False and r["steps"] == 5 and r["warmup"] == 1 and r["staged_batches"] == 3 and r["value"] > 0 and r["ms_per_step"] > 0
+    assert not set(r) & {"roofline", "cpu_baseline", "golden", "tick_latency", "adverse_mix", "pcie_inclusive"}
+    c = r["counters"]
+    assert c["rows"] == 5 * 4 * 256 and c["asserts"] == 0 and c["dropped_stale"] == 0 and c["need_host"] == 0
+    assert r["config"]["decisions_per_step_per_gpu"] * 5 <= c["rows"] and lines[1]["counters"] == c
+    names = sorted(os.listdir(dumps[0]))
+    assert "out_flags.npy" in names and "state_current_term.npy" in names and "rows.npy" in names
+    assert names == sorted(os.listdir(dumps[1])) and sum(os.path.getsize(dumps[0] / n) for n in names) <= 64 << 20
+    for n in names:
+        a, b = np.load(dumps[0] / n), np.load(dumps[1] / n)
+        assert a.dtype == np.float64 and np.array_equal(a, b), n
+    # the dump is the LAST timed step's: warm-up 0, timed 1 2 | reload | 0 1 2 — batch 2 of the stream on the state batches 0 and 1 left, as the oracle
+    # replays it; the step before it (batch 1) and the initial state differ
+    from rafting_amd import workload
+    from tests import oracle_lib
+    cfg = workload.config(3, 256)
+    gen = workload.ReplayGenerator(cfg, first_gid=0, count=256)
+    st0 = gen.initial_state()
+    orc = oracle_lib.OracleTable(256, cfg.cluster, cfg.self_slot, cfg.pre_vote)
+    orc.load_state(st0)
+    outs = [orc.submit(gen.next_batch(4)) for _ in range(3)]
+    st = orc.read_state()
+    orc.close()
+    got = lambda n: np.load(dumps[0] / (n + ".npy"))                              # noqa: E731
+    assert np.array_equal(got("rows"), np.arange(4 * 256)) and np.array_equal(got("groups"), np.arange(256))
+    for f in st.fields():
+        assert np.array_equal(got("state_" + f), getattr(st, f).astype(np.float64)), f
+    for f in ("resp_term", "flags"):
+        assert np.array_equal(got("out_" + f), outs[2].reply[f].astype(np.float64)), f
+    assert not np.array_equal(got("out_flags"), outs[1].reply["flags"].astype(np.float64))
+    assert not np.array_equal(got("state_commit_index"), st0.commit_index.astype(np.float64))

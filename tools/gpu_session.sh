@@ -4,7 +4,7 @@
 TAG=$1; shift
 OUT=gpurun_out/$TAG; mkdir -p $OUT
 export TMPDIR=/tmp
-B="python bench.py --no-cpu-baseline --no-pcie --index-base-batches 0 --tick-batches 0 --long-launch-rounds 0"
+B="python bench.py --full --no-cpu-baseline --no-pcie --index-base-batches 0 --tick-batches 0 --long-launch-rounds 0"
 line() { python -c "
 import json,sys
 for l in sys.stdin:
@@ -64,11 +64,11 @@ for step in "$@"; do
         timeout 120 build/ingress_bench 65536 16 16 1,2,4,8,16 > $OUT/ingress_bench.txt 2>&1; tail -n 5 $OUT/ingress_bench.txt ;;
     sweep) for R in 1 4 16 64; do $B --steps 20 --warmup 3 --rounds $R 2>>$OUT/aux.err | tee -a $OUT/rounds.jsonl | line rounds=$R; done
         $B --steps 10 --warmup 2 --override "p_conflict=0.005" 2>>$OUT/aux.err | tee -a $OUT/conflict.jsonl | line p_conflict=0.005 ;;
-    final) python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; cat $OUT/bench_default.json | line default
+    final) python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; cat $OUT/bench_default.json | line default
         python -c "import json; d=json.load(open('$OUT/bench_default.json')); r=d['roofline']; print('traffic', r['traffic'], 'hbm_frac_measured', r['hbm_frac_measured'], 'frac', r['frac'])"
         timeout 200 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.txt 2>&1; tail -n 1 $OUT/smoke.txt
         timeout 500 python tools/soak.py ${SOAK_SECONDS:-300} > $OUT/soak.txt 2>&1; tail -n 1 $OUT/soak.txt ;;
-    bench) python bench.py --steps 20 --warmup 5 > $OUT/bench_default.json 2> $OUT/bench_default.err; cat $OUT/bench_default.json | line default ;;
+    bench) python bench.py --full --steps 20 --warmup 5 > $OUT/bench_default.json 2> $OUT/bench_default.err; cat $OUT/bench_default.json | line default ;;
     hwid) for C in "--config 3" "--config 4" "--config 2" "--config 5 --groups-per-gpu 65536"; do     # where the dispatcher puts the deciding / I/O wavefronts (tools/placement.py)
           T=$(echo $C | tr -d ' -'); RG_DUMP_COUNTERS=$OUT/hwid_$T.bin RG_LIB=$(pwd)/rafting_amd/libraftgpu_hwid.so $B --steps 10 --warmup 2 $C 2>>$OUT/hwid.err | tee -a $OUT/hwid.jsonl | line "hwid $C"
           python tools/placement.py $OUT/hwid_$T.bin | tee -a $OUT/placement.txt; done ;;

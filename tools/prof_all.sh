@@ -9,10 +9,10 @@ TAG=$1
 ROOT=$(pwd)
 OUT=$ROOT/gpurun_out
 bash tools/prof.sh $TAG > $OUT/prof_$TAG.log 2>&1
-python bench.py --copy-bw > $OUT/bench_${TAG}_c3.json 2> $OUT/bench_${TAG}_c3.err
+python bench.py --full --copy-bw > $OUT/bench_${TAG}_c3.json 2> $OUT/bench_${TAG}_c3.err
 for spec in "2 4096" "4 131072" "5 131072" "5 65536"; do
   set -- $spec
-  python bench.py --config $1 --groups-per-gpu $2 --no-cpu-baseline --no-pcie > $OUT/bench_${TAG}_c$1_$2.json 2> $OUT/bench_${TAG}_c$1_$2.err
+  python bench.py --full --config $1 --groups-per-gpu $2 --no-cpu-baseline --no-pcie > $OUT/bench_${TAG}_c$1_$2.json 2> $OUT/bench_${TAG}_c$1_$2.err
   bash tools/prof.sh ${TAG}_c$1_$2 --config $1 --groups-per-gpu $2 > $OUT/prof_${TAG}_c$1_$2.log 2>&1      # kernel trace + the PMC passes (HBM bytes) for this workload too
 done
 python tools/bench_replicate.py 1048576 50 > $OUT/bench_${TAG}_repl.json 2> $OUT/bench_${TAG}_repl.err

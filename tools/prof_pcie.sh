@@ -3,7 +3,7 @@
 #   tools/prof_pcie.sh <tag> [events to print, default 70]
 ROOT=$(pwd); OUT=$ROOT/gpurun_out/prof_pcie_$1; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $OUT -o t -- python $ROOT/bench.py --no-cpu-baseline --steps 2 --warmup 1 --pcie-batches 6 > $OUT/run.log 2>&1
+rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $OUT -o t -- python $ROOT/bench.py --full --no-cpu-baseline --steps 2 --warmup 1 --pcie-batches 6 > $OUT/run.log 2>&1
 cd $ROOT
 python - $OUT ${2:-70} <<'PY'
 import csv, glob, sys
