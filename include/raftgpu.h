@@ -57,10 +57,11 @@
 extern "C" {
 #endif
 
-#define RG_ABI_VERSION      5     /* 2: RG_EV_IS_REQ, RG_EV_TIMEOUT.aux fence, RG_F_TIMER_MUTED, rg_timers_expired_epochs, rg_submit_async(_packed), 48-byte rg_send_head_t
+#define RG_ABI_VERSION      6     /* 2: RG_EV_IS_REQ, RG_EV_TIMEOUT.aux fence, RG_F_TIMER_MUTED, rg_timers_expired_epochs, rg_submit_async(_packed), 48-byte rg_send_head_t
                                      3: rg_submit32 / rg_batch32_pack, RG_HDR_SAME_TERM in rg_batch32_t rows
                                      4: compact OUTCOME rows (rg_out32_t, rg_submit32c, rg_outcome32_unpack, RG_F_WIDE_VALUES); rg_table_option; the index base of the compact formats (rg_index_base_set)
-                                     5: the device-resident tick on compact outcome rows: rg_timers_update32, rg_health_update32, rg_tick2_*; clusters of up to 15 nodes */
+                                     5: the device-resident tick on compact outcome rows: rg_timers_update32, rg_health_update32, rg_tick2_*; clusters of up to 15 nodes
+                                     6: automatic index bases: RG_OPT_AUTO_INDEX_BASE, rg_index_base_advance / rg_index_base_advance32 */
 #define RG_MIN_CLUSTER      2     /* P: cluster size incl. self (RaftCluster.size()) */
 #define RG_MAX_CLUSTER      15    /* (ABI 5; the slot field of a row header is 4 bits. Leadership.majorIndices sorts any number of followers, member/Leadership.java:116-130.)
                                      Clusters of up to RG_MAX_COMPACT_CLUSTER nodes have every kernel; larger ones are decided by the wide-row kernels only:
@@ -274,7 +275,10 @@ const char *rg_last_error(const rg_table_t *t);      /* t may be NULL for create
  * context.participant() BEFORE the event loop sees the task (context/RaftRoutine.java:65-77); a serial engine can only reproduce that when the
  * row names the participant whose ticket fired (rg_timers_expired_epochs supplies it) — the ordering contract of INTEGRATION.md section 1,
  * enforced instead of merely stated. The C++ host's IngressFlusher turns it on. */
-enum { RG_OPT_REQUIRE_FENCED_TIMEOUTS = 1 };
+enum { RG_OPT_REQUIRE_FENCED_TIMEOUTS = 1,
+       RG_OPT_AUTO_INDEX_BASE = 2 };        /* (ABI 6) value = the window W of the automatic index bases: 0 = off (default), 1 <= W < 2^30 = on, anything else -1.
+                                               See "THE INDEX BASE OF THE COMPACT FORMATS" below. Switching it on or off bumps what a recorded tick has baked in:
+                                               rg_tick_launch / rg_tick2_launch of an earlier recording then refuse (-1). Recommended window: 2^28. */
 int         rg_table_option(rg_table_t *t, int option, int value);
 uint32_t    rg_table_groups(const rg_table_t *t);
 uint32_t    rg_table_cluster(const rg_table_t *t);
@@ -391,8 +395,27 @@ int64_t rg_batch32_pack(const rg_batch_t *in, rg_ev_head_t *head, rg_ev_quad32_t
  * (RaftLog.flush, command/storage/RocksLog.java:228-242) between two launches; a group whose epoch.index is 0 keeps base 0. Decisions never depend
  * on the base: the 32-bit body works on the relative image while every non-zero index of the group lies in (base, base + 2^30) and epoch.index > base,
  * the 64-bit body on absolute values otherwise (a value without an image in an rg_out32_t row: RG_F_WIDE_VALUES). base = 0 is ABI 3's format. */
+/* AUTOMATIC BASES (ABI 6). With RG_OPT_AUTO_INDEX_BASE = W the table moves the bases itself, so that a host which packs its rows relative to a mirror
+ * of them never has to call rg_index_base_set after a compaction. The rule:
+ *       every RG_EV_LOG_FLUSH row a submission carries for group g, WHATEVER ITS STATUS (RG_FLUSH_OUT_OF_BOUNDS, RG_SKIPPED_AFTER_NEED_HOST and RG_NEED_HOST
+ *       included), raises base[g] to max(base[g], a - W), a = the row's flush index in ABSOLUTE terms (a compact row's a is relative to the base the launch
+ *       STARTED with; a = 0 moves nothing). All rows and outcome rows of a launch stay relative to the bases the launch started with; the new bases apply
+ *       from the next launch (the next replay, for a recorded tick).
+ * It depends on the rows only, never on outcomes: a host works out the bases of batch k + 1 before batch k is decided (rg_index_base_advance* below), which
+ * is what two batches in flight need. Every submission path applies it — rg_submit / rg_submit_async (wide rows: absolute a), rg_submit32, rg_submit32c,
+ * rg_submit_async_packed, rg_tick_*, rg_tick2_*, host and device memory alike. Nothing else moves a base: rg_load_state leaves the bases alone, rg_index_base_set
+ * still sets them and the automatic moves go on from there, and the rule never lowers one. Decisions never depend on it (every reply, effect and persist row
+ * is the one without it); it only decides which body decides a workgroup, and what rg_index_base_get reports. A group whose state falls outside
+ * (base, base + 2^30) after a move — a lagging follower's non-zero matchIndex at a leader, say — is decided by the 64-bit body, correctly. W is how far
+ * below the newest flush a stale row's index may lie and still have a relative image: 2^28 is the recommended value. */
 int rg_index_base_set(rg_table_t *t, uint32_t first, uint32_t count, const int64_t *base);
 int rg_index_base_get(rg_table_t *t, uint32_t first, uint32_t count, int64_t *base);
+/* Host-side (no device involved): the rule above applied IN PLACE to a caller's mirror index_base[groups] for one batch, every round, dense (count == groups)
+ * or sparse (rounds == 1, gid < groups). rg_index_base_advance takes wide rows (absolute a); rg_index_base_advance32 compact rows, whose a is relative to the
+ * array AS IT IS ON ENTRY. window: as RG_OPT_AUTO_INDEX_BASE, 1 <= W < 2^30. Returns 0; -1 a missing column (head, ab / abcd, index_base) or a window out of
+ * range; -2 a batch of another shape (count, gid, rounds). */
+int rg_index_base_advance(const rg_batch_t *in, int32_t window, uint32_t groups, int64_t *index_base);
+int rg_index_base_advance32(const rg_batch32_t *in, int32_t window, uint32_t groups, int64_t *index_base);
 /* rg_batch32_pack with bases: index_base[g] for every group of the table (NULL: all 0); -3 also when an index lies at or below its group's base */
 int64_t rg_batch32_pack_rel(const rg_batch_t *in, const int64_t *index_base, rg_ev_head_t *head, rg_ev_quad32_t *abcd, int32_t *entry_terms);
 /* COMPACT OUTCOME ROWS (ABI 4). What a reply carries is RaftResponse(term, success) (RaftResponse.java:8-24) plus instructions; while a
@@ -426,7 +449,8 @@ int rg_submit32c(rg_table_t *t, const rg_batch32_t *in, const rg_outcome32_t *ou
  * epoch of every group BEFORE the batch (rg_group_state_t.role_epoch); updated in place to the epochs after it. Rows flagged
  * RG_F_WIDE_VALUES are copied from in->wide (-3 when that is missing). Returns 0, or < 0. */
 int rg_outcome32_unpack(const rg_outcome32_t *in, uint32_t rounds, uint32_t count, uint32_t *role_epoch, const rg_outcome_t *out);
-/* the same for a table with index bases (below): index_base[count] puts commit_index / log_from back on the groups' bases (NULL: all 0) */
+/* the same for a table with index bases (below): index_base[count] puts commit_index / log_from back on the groups' bases (NULL: all 0) — the bases the
+ * batch was PACKED with, i.e. those at the start of its launch (with RG_OPT_AUTO_INDEX_BASE the table may have moved them by the time the rows arrive) */
 int rg_outcome32_unpack_rel(const rg_outcome32_t *in, uint32_t rounds, uint32_t count, uint32_t *role_epoch, const int64_t *index_base, const rg_outcome_t *out);
 /* which step kernel a batch of `count` rows per round is decided by: "rg::step_split_kernel" (a deciding and an I/O
  * wavefront per 64 groups; chosen while the batch has at most one wavefront of groups per SIMD) or "rg::step_kernel";

@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 MIN_CLUSTER, MAX_CLUSTER, MAX_COMPACT_CLUSTER = 2, 15, 7
 TERM_RUNS = 4
 NO_NODE = -1
@@ -42,6 +42,7 @@ NEED_HOST, SKIPPED_AFTER_NEED_HOST, BAD_EVENT, UNSUPPORTED_LOG_STATE = 32, 33, 3
 
 MEM_HOST, MEM_DEVICE = 0, 1
 OPT_REQUIRE_FENCED_TIMEOUTS = 1
+OPT_AUTO_INDEX_BASE = 2              # (ABI 6) window W of the automatic index bases, 0 = off; 2^28 recommended (include/raftgpu.h)
 NUM_COUNTERS = 8
 
 HEAD_DT = np.dtype([("hdr", "<u4"), ("aux", "<u4")])

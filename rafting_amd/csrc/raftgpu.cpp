@@ -62,7 +62,8 @@ struct rg_table {
     int fast_paths = 1;                         // RG_FAST=0: general handlers only (differential tests)
     int force_wide = 0;                         // RG_FORCE_WIDE=1: the compact-format kernel skips its 32-bit body (differential tests)
     int require_fence = 0;                      // rg_table_option(RG_OPT_REQUIRE_FENCED_TIMEOUTS)
-    int has_bases = 0;                          // rg_index_base_set has stored a non-zero base at some time
+    int has_bases = 0;                          // rg_index_base_set has stored a non-zero base at some time (or RG_OPT_AUTO_INDEX_BASE was switched on)
+    int auto_window = 0;                        // rg_table_option(RG_OPT_AUTO_INDEX_BASE): 0 = off
     Staging st_abcd32, st_terms32, st_out32, st_persist32;
     int lanes = -1;                             // -1: pick per launch; 0: split kernel; 64: single-wavefront kernel (RG_SPLIT env forces one)
     uint32_t simds = 1024;                      // SIMDs of the device (CUs x 4)
@@ -168,6 +169,12 @@ int rg_table_option(rg_table_t *t, int option, int value)
     case RG_OPT_REQUIRE_FENCED_TIMEOUTS:
         if (t->require_fence != (value != 0)) t->config_gen += 1;       // (a recorded tick has the old value baked in: rg_tick_launch refuses it)
         t->require_fence = value != 0;
+        return 0;
+    case RG_OPT_AUTO_INDEX_BASE:
+        if (value < 0 || value >= (1 << 30)) return fail(t, -1, "rg_table_option: RG_OPT_AUTO_INDEX_BASE window %d outside [0, 2^30)", value);
+        if (t->auto_window != value) t->config_gen += 1;                // (the window is baked into a recorded launch like every option)
+        if (value != 0 && !t->has_bases) t->has_bases = 1;              // (the kernels read the base column from now on)
+        t->auto_window = value;
         return 0;
     default: return fail(t, -1, "rg_table_option: unknown option %d", option);
     }
@@ -517,6 +524,7 @@ static rg::StepParams step_params(rg_table *t, const rg_batch_t *in)
     p.force_wide = t->force_wide;
     p.require_fence = t->require_fence;
     p.has_bases = t->has_bases;
+    p.auto_window = t->auto_window;
     return p;
 }
 
@@ -1121,6 +1129,47 @@ int rg_index_base_get(rg_table_t *t, uint32_t first, uint32_t count, int64_t *ba
     HIP_TRY(t, hipMemcpyAsync(base, t->dt.ibase + first, (size_t)count * sizeof(int64_t), hipMemcpyDeviceToHost, t->stream));
     HIP_TRY(t, hipStreamSynchronize(t->stream));
     return 0;
+}
+
+/* RG_OPT_AUTO_INDEX_BASE's rule on a caller's mirror (no device involved): see include/raftgpu.h. flush(row) -> the row's flush index in absolute terms. */
+extern "C++" template <class Flush>
+int advance_bases(uint32_t rounds, uint32_t count, const uint32_t *gid, const rg_ev_head_t *head, int32_t window, uint32_t groups, int64_t *index_base,
+                         Flush flush)
+{
+    if (!head || !index_base || window < 1 || window >= (1 << 30)) return -1;
+    if (gid ? (rounds != 1 || count > groups) : count != groups) return -2;
+    if (gid)
+        for (uint32_t i = 0; i < count; i++)
+            if (gid[i] >= groups) return -2;
+    // every a of the batch is taken against the array as it is on entry: the per-group maxima first, then the moves
+    std::vector<int64_t> top(gid ? count : groups, 0);
+    for (uint32_t r = 0; r < rounds; r++)
+        for (uint32_t i = 0; i < count; i++) {
+            const size_t row = (size_t)r * count + i;
+            if (RG_HDR_KIND(head[row].hdr) != RG_EV_LOG_FLUSH) continue;
+            const int64_t a = flush(row, gid ? gid[i] : i);
+            if (a > top[i]) top[i] = a;
+        }
+    for (uint32_t i = 0; i < (uint32_t)top.size(); i++) {
+        int64_t &base = index_base[gid ? gid[i] : i];
+        if (top[i] - window > base) base = top[i] - window;
+    }
+    return 0;
+}
+
+int rg_index_base_advance(const rg_batch_t *in, int32_t window, uint32_t groups, int64_t *index_base)
+{
+    if (!in || !in->ab) return -1;
+    return advance_bases(in->rounds, in->count, in->gid, in->head, window, groups, index_base, [&](size_t row, uint32_t) { return (int64_t)in->ab[row].x; });
+}
+
+int rg_index_base_advance32(const rg_batch32_t *in, int32_t window, uint32_t groups, int64_t *index_base)
+{
+    if (!in || !in->abcd) return -1;
+    return advance_bases(in->rounds, in->count, in->gid, in->head, window, groups, index_base, [&](size_t row, uint32_t g) {
+        const int32_t a = in->abcd[row].a;
+        return a <= 0 ? (int64_t)0 : (int64_t)a + index_base[g];      // (read before any move: the moves come after the whole batch; a < 0 is no index)
+    });
 }
 
 /* which of a row's fields a, b, c, d (bits 0..3) are log indices (rg_device.hpp: index_fields) */

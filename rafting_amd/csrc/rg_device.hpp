@@ -95,6 +95,7 @@ struct StepParams {
     int32_t force_wide;             // compact-format kernel: skip the 32-bit body (tests)
     int32_t require_fence;          // RG_OPT_REQUIRE_FENCED_TIMEOUTS: a TIMEOUT row with aux == 0 is RG_BAD_EVENT
     int32_t has_bases;              // the host has set a non-zero index base at some time (rg_index_base_set): 0 = the ibase column is all zero and is not read
+    int32_t auto_window;            // RG_OPT_AUTO_INDEX_BASE: W > 0 raises a group's base to max(base, a - W) for every LOG_FLUSH row (absolute a), from the next launch on
 };
 
 struct ReplicateParams {             // N1: Leader.replicateLog for many groups (rg_kernels.hip: replicate_kernel)
@@ -379,6 +380,13 @@ __device__ __forceinline__ bool fits32(const Group &g, uint32_t limit)
 // fit sends the workgroup to the 64-bit body as before. base = 0 (the default) is the format of ABI 3, bit for bit.
 __device__ __forceinline__ int64_t to_rel(int64_t x, int64_t base) { const int64_t d = x - base; return x == 0 ? 0 : (d == 0 ? -1 : d); }      // (x == base != 0 has no image: -1 fails every range check)
 __device__ __forceinline__ int64_t to_abs(int64_t r, int64_t base) { return r == 0 ? 0 : r + base; }
+// RG_OPT_AUTO_INDEX_BASE (include/raftgpu.h): flush_max = the largest absolute flush index of the group's LOG_FLUSH rows in this launch (0: none), base = the
+// group's base at launch start. Written where the group's state is committed, after every row of the launch was decided on the old base.
+__device__ __forceinline__ void advance_base(const StepParams &p, uint32_t gi, int64_t base, int64_t flush_max)
+{
+    const int64_t w = p.auto_window;
+    if (flush_max - w > base) p.t.ibase[gi] = flush_max - w;
+}
 template <class Fn> __device__ __forceinline__ Group map_indices(const Group &g, Fn f)
 {
     Group r = g;

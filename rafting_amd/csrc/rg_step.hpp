@@ -400,6 +400,7 @@ __global__ __launch_bounds__(BLOCK, 1) void step_kernel(const StepParams p)
     const bool FAST = p.fast_paths != 0;                 // RG_FAST=0 forces every row through the general handlers (tests)
     Tally tally;
     bool blocked = false;
+    int64_t flush_max = 0;                               // RG_OPT_AUTO_INDEX_BASE: the largest flush index of the group's rows (wide rows: absolute)
 
     // outcome of the previous round, stored one round late (see the drain below)
     rg_reply_t pend_rep{0, 0u, 0u};
@@ -434,6 +435,7 @@ __global__ __launch_bounds__(BLOCK, 1) void step_kernel(const StepParams p)
             // every lane goes through tier 1: it contains wave-uniform branches on ballots and is therefore called from converged
             // code; a lane blocked after a NEED_HOST simply asks for nothing
             const bool skip = blocked & (kind != RG_EV_NONE);
+            flush_max = ((kind == RG_EV_LOG_FLUSH) & (cur.a > flush_max)) ? cur.a : flush_max;      // (skipped rows count too)
             const uint32_t hdr = decorate<false>(p, cur, cur_t, false);
             const bool done = tier1<F, int64_t, PeersWide<F>>(p, g, pe, st.fx, FAST & !skip, hdr, cur.aux, cur.a, cur.b, cur.c, cur.d, cur_t.e0);
             bool slow = !done & !skip;
@@ -467,7 +469,10 @@ __global__ __launch_bounds__(BLOCK, 1) void step_kernel(const StepParams p)
         if (pend_w_per) nt_store16(p.persist + row, pend_per);
     }
 
-    if (active) store_group(p.t, gi, g, pe, F);
+    if (active) {
+        store_group(p.t, gi, g, pe, F);
+        if (p.auto_window != 0) advance_base(p, gi, p.t.ibase[gi], flush_max);
+    }
     tally.flush(p, lane, active);
 }
 
@@ -502,7 +507,9 @@ struct SplitLds {
     // 64-bit body
     static constexpr int EVF = EV32 ? (int)EV_D + 1 : (int)EV_FIELDS;
     static constexpr size_t W_EPOCH = 0, W_NEXT = W_EPOCH + F * BLOCK * 8, W_MATCH = W_NEXT + F * BLOCK * 8, W_REJ = W_MATCH + F * BLOCK * 8,
-                            W_EV = W_REJ + F * BLOCK * 4, W_OUT = W_EV + 2 * EVF * BLOCK * 8, W_END = W_OUT + 2 * OUT_FIELDS * BLOCK * 8;
+                            W_EV = W_REJ + F * BLOCK * 4, W_OUT = W_EV + 2 * EVF * BLOCK * 8, W_AUTO = W_OUT + 2 * OUT_FIELDS * BLOCK * 8,
+                            W_END = W_AUTO + BLOCK * 24;      // W_AUTO: the deciding wavefront's {running max, base slot, window} of RG_OPT_AUTO_INDEX_BASE. On compact
+                                                              // rows this lies within N_END up to F = 5; at F = 6 it adds 496 B (23 552 B per workgroup)
     // 32-bit body: follower records, their matchIndex row, a four-slot event ring (written two rounds ahead), a two-slot outcome ring, the I/O
     // wavefront's tables: class word by (kind, slot), flags by predicate word (19 KB in all: eight workgroups per CU still fit)
     static constexpr int MV = (F + 3) / 4;
@@ -647,6 +654,13 @@ __device__ __forceinline__ void split_body(const StepParams &p, unsigned char *s
     Stepper<F, PeersWide<F>> st(p, g, pe);
     const bool FAST = p.fast_paths != 0;
     bool blocked = false;
+    // RG_OPT_AUTO_INDEX_BASE: the largest flush index of the group's LOG_FLUSH rows (absolute: the I/O wavefront converted compact rows), where the new base
+    // goes (0: nowhere) and the window, all three in LDS — live in registers across the round loop any of them pushes the 64-bit kernels past their
+    // register budgets (they then reserve scratch)
+    int64_t *sh_flush = reinterpret_cast<int64_t *>(smem + L::W_AUTO) + 3 * lane;
+    sh_flush[0] = 0;
+    sh_flush[1] = (active & (p.auto_window != 0)) ? (int64_t)reinterpret_cast<uint64_t>(p.t.ibase + gi) : 0;
+    sh_flush[2] = p.auto_window;
     lds_barrier();                                       // event 0 is visible
     for (uint32_t r = 0; r < p.rounds; r++) {
         const uint32_t slot = r & 1u;
@@ -657,6 +671,8 @@ __device__ __forceinline__ void split_body(const StepParams &p, unsigned char *s
         int64_t e0 = (int64_t)(int32_t)aux;              // compact rows: the term shared by the carried entries travels in aux
         if constexpr (!EV32) e0 = (int64_t)sh_ev[slot][EV_E0][lane];
         const uint32_t kind = RG_HDR_KIND(hdr);
+        { const int64_t top = *sh_flush; *sh_flush = ((kind == RG_EV_LOG_FLUSH) & (a > top)) ? a : top; }      // (skipped rows count too; no branch: an exec mask saved
+                                                                                                               //  inside the loop costs this body its SGPR budget)
         // tier 1 branches on wavefront ballots: every lane calls it (a lane blocked after a NEED_HOST asks for nothing)
         const bool skip = blocked & (kind != RG_EV_NONE);
         const bool done = tier1<F, int64_t, PeersWide<F>>(p, g, pe, st.fx, FAST & !skip, hdr, aux, a, b, c, d, e0);
@@ -692,6 +708,11 @@ __device__ __forceinline__ void split_body(const StepParams &p, unsigned char *s
     uint32_t gi_out = gi;
     RG_FRESH_VGPR(gi_out);
     if (active) store_group(p.t, gi_out, g, pe, F);
+    if (const int64_t at = sh_flush[1]; at != 0) {      // (advance_base's rule, on what waits in LDS)
+        RG_GLOBAL_AS int64_t *slot = reinterpret_cast<RG_GLOBAL_AS int64_t *>((uint64_t)at);
+        const int64_t top = sh_flush[0], window = sh_flush[2];
+        if (top - window > *slot) *slot = top - window;
+    }
 }
 
 template <int F, bool SPARSE>
@@ -998,6 +1019,9 @@ __device__ __forceinline__ bool narrow_body(const StepParams &p, unsigned char *
         pe.base = base;
         Group g64;
         load_group(p.t, gi, g64);
+        // run slots 1..3 at or beyond the run count are left-overs — RaftLog.flush empties a log and keeps them — that nothing reads (refresh_tail: slots
+        // below max(rc, 1); rg_read_state reports zeros): left in, they hold a group whose base has moved past them out of the 32-bit image
+        g64.s1 = g64.rc > 1 ? g64.s1 : 0; g64.s2 = g64.rc > 2 ? g64.s2 : 0; g64.s3 = g64.rc > 3 ? g64.s3 : 0;
         if (any_base) g64 = group_to_rel(g64, base);
         // (role epochs grow by at most two per round: a launch of fewer than 2^24 rounds cannot take one out of s_ne()'s domain;
         //  with a base the epoch must lie above it: the one index tier 1 computes from — prepareReplication's epoch.index + 1 — is then never "0 + 1")
@@ -1010,6 +1034,9 @@ __device__ __forceinline__ bool narrow_body(const StepParams &p, unsigned char *
     bool bailed = __builtin_amdgcn_ballot_w64(!in_domain) != 0;
     if (lane == 0) *sh_bail = bailed ? 1u : 0u;
     bool blocked = false;
+    // RG_OPT_AUTO_INDEX_BASE: the largest flush index of the group's LOG_FLUSH rows, RELATIVE to the base (0: none). Every such row is open after tier 1
+    // (tier 1 decides no LOG_FLUSH), so it is kept in the general branch below, off the tier-1 spine.
+    int32_t flush_max = 0;
     lds_barrier();
     if (bailed) return false;
     RG_PROBE_BEGIN();
@@ -1040,12 +1067,15 @@ __device__ __forceinline__ bool narrow_body(const StepParams &p, unsigned char *
             // (the header as loaded, KIND_OUT_OF_DOMAIN apart; the general handlers expect the same-term mark where decorate<true> puts it)
             const uint32_t hdr = ((uint32_t)h.w & ~(7u << 9)) | ((((uint32_t)h.w & RG_HDR_SAME_TERM) != 0) ? HDR_SAME_IN : 0u), aux = (uint32_t)h.y, kind = RG_HDR_KIND(hdr);
             const bool skip = open & blocked & (kind != RG_EV_NONE);
+            flush_max = (open & (kind == RG_EV_LOG_FLUSH) & (q.x > flush_max)) ? q.x : flush_max;      // (skipped rows count too)
             // tier 1.5 (rg_tier1n.hpp): four row classes an election or a cache miss leaves behind, decided on the 32-bit image without widening it
             bool park;
             const bool slow = open & !skip & !tier15<F>(p, g, pe, out, park, open & !skip, h.x, h.y, h.z, q.x, q.y, q.z, q.w);
             if (park) { blocked = true; g.nallow = -1; g.recache(); }
             RG_NOTE_SLOW(slow, lane == 0);                  // (the host emulation counts the rows and wave-rounds that reach the general handlers)
-            bool bail = slow & (kind == KIND_OUT_OF_DOMAIN);
+            // (a skipped row outside the domain has lost its kind to KIND_OUT_OF_DOMAIN: with automatic bases it may have been a LOG_FLUSH whose index
+            //  this body cannot hold — the 64-bit body redoes the workgroup and sees it)
+            bool bail = (slow | (skip & (p.auto_window != 0))) & (kind == KIND_OUT_OF_DOMAIN);
             if (slow & !bail) {
                 // the general handlers decide on ABSOLUTE values: the image and the row's index fields are taken off the base, the results put back on it
                 const int64_t base = any_base ? *sh_base : 0;
@@ -1120,6 +1150,10 @@ __device__ __forceinline__ bool narrow_body(const StepParams &p, unsigned char *
         uint32_t gi_out = gi;
         RG_FRESH_VGPR(gi_out);
         store_group(p.t, gi_out, g64, pe, F);       // (pe's scalar accessors return absolute values)
+        if (p.auto_window != 0) {
+            const int64_t base = *sh_base;
+            advance_base(p, gi_out, base, to_abs(flush_max, base));
+        }
     }
     return true;
 }

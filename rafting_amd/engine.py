@@ -31,7 +31,7 @@ def exported_symbols():
     """Every entry point include/raftgpu.h declares."""
     return [
         "rg_abi_version", "rg_table_create", "rg_table_destroy", "rg_last_error", "rg_table_groups",
-        "rg_table_cluster", "rg_table_option", "rg_load_state", "rg_read_state", "rg_submit", "rg_submit32", "rg_submit32c", "rg_outcome32_unpack", "rg_outcome32_unpack_rel", "rg_index_base_set", "rg_index_base_get", "rg_batch32_pack_rel", "rg_batch32_pack", "rg_submit_async", "rg_submit_async_packed", "rg_submit_wait", "rg_tick_create", "rg_tick_launch", "rg_tick_wait", "rg_tick_destroy", "rg_tick2_create", "rg_tick2_launch", "rg_tick2_wait", "rg_tick2_destroy", "rg_timers_update32", "rg_health_update32", "rg_sync", "rg_step_kernel", "rg_host_alloc", "rg_host_free", "rg_dev_alloc",
+        "rg_table_cluster", "rg_table_option", "rg_load_state", "rg_read_state", "rg_submit", "rg_submit32", "rg_submit32c", "rg_outcome32_unpack", "rg_outcome32_unpack_rel", "rg_index_base_set", "rg_index_base_get", "rg_index_base_advance", "rg_index_base_advance32", "rg_batch32_pack_rel", "rg_batch32_pack", "rg_submit_async", "rg_submit_async_packed", "rg_submit_wait", "rg_tick_create", "rg_tick_launch", "rg_tick_wait", "rg_tick_destroy", "rg_tick2_create", "rg_tick2_launch", "rg_tick2_wait", "rg_tick2_destroy", "rg_timers_update32", "rg_health_update32", "rg_sync", "rg_step_kernel", "rg_host_alloc", "rg_host_free", "rg_dev_alloc",
         "rg_dev_free", "rg_copy_to_device", "rg_copy_to_host", "rg_stream", "rg_replicate", "rg_timers_configure", "rg_timers_update",
         "rg_timers_expired", "rg_timers_expired_epochs", "rg_timers_arm", "rg_timers_read", "rg_health_update", "rg_health_failure", "rg_ready", "rg_health_read",
         "rg_timing_enable",
@@ -109,6 +109,8 @@ def lib():
         L.rg_outcome32_unpack_rel.argtypes = [C.POINTER(abi.COutcome32), u32, u32, vp, vp, C.POINTER(abi.COutcome)]
         L.rg_index_base_set.argtypes = [vp, u32, u32, vp]
         L.rg_index_base_get.argtypes = [vp, u32, u32, vp]
+        L.rg_index_base_advance.argtypes = [C.POINTER(abi.CBatch), i32, u32, vp]
+        L.rg_index_base_advance32.argtypes = [C.POINTER(abi.CBatch32), i32, u32, vp]
         L.rg_batch32_pack_rel.restype = C.c_int64
         L.rg_batch32_pack_rel.argtypes = [C.POINTER(abi.CBatch), vp, vp, vp, vp]
         L.rg_batch32_pack.restype = C.c_int64
@@ -173,6 +175,20 @@ def _replicate(call, groups, cluster, gid, heartbeat, in_flight):
     ptr = lambda a: None if a is None else a.ctypes.data   # noqa: E731
     call(count, ptr(gid), ptr(hb), ptr(fl), head.ctypes.data, send.ctypes.data)
     return head, np.ascontiguousarray(send.reshape(F, count).T)
+
+
+def advance_index_base(batch, base, window):
+    """RG_OPT_AUTO_INDEX_BASE's rule on a host mirror (rg_index_base_advance / rg_index_base_advance32, no device involved): every LOG_FLUSH row of
+    `batch` raises its group's base to max(base, a - window). abi.Batch: a absolute; abi.Batch32: a relative to `base` as passed in. `base` is an
+    int64 array with one entry per group of the table, updated in place (and returned)."""
+    if not (isinstance(base, np.ndarray) and base.dtype == np.int64 and base.flags["C_CONTIGUOUS"]):
+        raise EngineError("advance_index_base: base must be a contiguous int64 array (it is updated in place)")
+    b = batch.as_struct()
+    fn = lib().rg_index_base_advance32 if isinstance(batch, abi.Batch32) else lib().rg_index_base_advance
+    rc = fn(C.byref(b), int(window), len(base), base.ctypes.data)
+    if rc != 0:
+        raise EngineError("advance_index_base: %d (%s)" % (rc, {-1: "missing column or window outside [1, 2^30)", -2: "batch shape does not fit the groups"}.get(rc, "?")))
+    return base
 
 
 def pack32(batch, index_base=None):
@@ -602,6 +618,11 @@ class Table:
         b = np.zeros(count, dtype=np.int64)
         self._check(lib().rg_index_base_get(self._h, first, count, b.ctypes.data))
         return b
+
+    def set_auto_index_base(self, window):
+        """rg_table_option(RG_OPT_AUTO_INDEX_BASE, window): with 1 <= window < 2^30 every LOG_FLUSH row raises its group's index base to
+        max(base, a - window) from the next launch on (advance_index_base is the same rule for a host mirror); 0 switches it off"""
+        self.set_option(abi.OPT_AUTO_INDEX_BASE, window)
 
     def set_option(self, option, value):
         """rg_table_option, e.g. (abi.OPT_REQUIRE_FENCED_TIMEOUTS, 1)"""
