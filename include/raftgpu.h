@@ -61,7 +61,8 @@ extern "C" {
                                      3: rg_submit32 / rg_batch32_pack, RG_HDR_SAME_TERM in rg_batch32_t rows
                                      4: compact OUTCOME rows (rg_out32_t, rg_submit32c, rg_outcome32_unpack, RG_F_WIDE_VALUES); rg_table_option; the index base of the compact formats (rg_index_base_set)
                                      5: the device-resident tick on compact outcome rows: rg_timers_update32, rg_health_update32, rg_tick2_*; clusters of up to 15 nodes
-                                     6: automatic index bases: RG_OPT_AUTO_INDEX_BASE, rg_index_base_advance / rg_index_base_advance32 */
+                                     6: automatic index bases: RG_OPT_AUTO_INDEX_BASE, rg_index_base_advance / rg_index_base_advance32
+                                        (still 6, new symbols only — nothing that existed changed: rg_submit32c_sparse, rg_tick2_rows_t, rg_tick2_create_sparse) */
 #define RG_MIN_CLUSTER      2     /* P: cluster size incl. self (RaftCluster.size()) */
 #define RG_MAX_CLUSTER      15    /* (ABI 5; the slot field of a row header is 4 bits. Leadership.majorIndices sorts any number of followers, member/Leadership.java:116-130.)
                                      Clusters of up to RG_MAX_COMPACT_CLUSTER nodes have every kernel; larger ones are decided by the wide-row kernels only:
@@ -402,8 +403,8 @@ int64_t rg_batch32_pack(const rg_batch_t *in, rg_ev_head_t *head, rg_ev_quad32_t
  *       STARTED with; a = 0 moves nothing). All rows and outcome rows of a launch stay relative to the bases the launch started with; the new bases apply
  *       from the next launch (the next replay, for a recorded tick).
  * It depends on the rows only, never on outcomes: a host works out the bases of batch k + 1 before batch k is decided (rg_index_base_advance* below), which
- * is what two batches in flight need. Every submission path applies it — rg_submit / rg_submit_async (wide rows: absolute a), rg_submit32, rg_submit32c,
- * rg_submit_async_packed, rg_tick_*, rg_tick2_*, host and device memory alike. Nothing else moves a base: rg_load_state leaves the bases alone, rg_index_base_set
+ * is what two batches in flight need. Every submission path applies it — rg_submit / rg_submit_async (wide rows: absolute a), rg_submit32, rg_submit32c, rg_submit32c_sparse,
+ * rg_submit_async_packed, rg_tick_*, rg_tick2_* (dense and sparse), host and device memory alike. Nothing else moves a base: rg_load_state leaves the bases alone, rg_index_base_set
  * still sets them and the automatic moves go on from there, and the rule never lowers one. Decisions never depend on it (every reply, effect and persist row
  * is the one without it); it only decides which body decides a workgroup, and what rg_index_base_get reports. A group whose state falls outside
  * (base, base + 2^30) after a move — a lagging follower's non-zero matchIndex at a leader, say — is decided by the 64-bit body, correctly. W is how far
@@ -434,8 +435,9 @@ int64_t rg_batch32_pack_rel(const rg_batch_t *in, const int64_t *index_base, rg_
  *                   see rg_submit32) puts the full rows of an event whose values do not fit — such a row carries RG_F_WIDE_VALUES and the
  *                   low 32 bits. The columns are not touched otherwise. Without them the full values of such a row are lost to the caller
  *                   (rg_read_state still has the group's state).
- * Same batches, same decisions, same table state as rg_submit32; dense batches only (gid == NULL). The device-side timers and health statistics
- * take these rows as they are: rg_timers_update32 / rg_health_update32 (ABI 5), or the whole tick as one graph: rg_tick2_*. */
+ * Same batches, same decisions, same table state as rg_submit32. rg_submit32c takes dense batches only (gid == NULL); a LIST of groups goes through
+ * rg_submit32c_sparse (below). The device-side timers and health statistics take the rows of a dense batch as they are: rg_timers_update32 /
+ * rg_health_update32 (ABI 5), or the whole tick as one graph: rg_tick2_* — dense, or for a list of groups (rg_tick2_create_sparse). */
 typedef struct { int32_t resp_term; uint32_t flags; int32_t commit_index; int32_t log_from; } rg_out32_t;          /* 16 B */
 typedef struct { int32_t term; int32_t voted_for; uint32_t role_epoch; int32_t role; } rg_persist32_t;            /* 16 B */
 typedef struct {
@@ -444,6 +446,13 @@ typedef struct {
     rg_outcome_t    wide;      /* optional overflow columns */
 } rg_outcome32_t;
 int rg_submit32c(rg_table_t *t, const rg_batch32_t *in, const rg_outcome32_t *out, int memspace);
+/* The same for a LIST of groups: compact rows of the groups in->gid names in, compact outcome rows out. in->gid is required (strictly ascending, each below the
+ * table's group count), rounds == 1, count <= groups; everything else as rg_submit32c — both memspaces, the overflow columns all three or none, RG_FORCE_WIDE,
+ * index bases: the indices of row i, in and out, are relative to the base of ITS group gid[i]. RG_MEM_HOST validates the list as rg_submit does, RG_MEM_DEVICE
+ * trusts it. Every outcome column holds `count` rows, row i for group gid[i]; groups the list does not name are not touched. The rows — after
+ * rg_outcome32_unpack(_rel) with the role epochs / index bases of the listed groups gathered per row — and the table state are those of rg_submit32 on the
+ * same batch. */
+int rg_submit32c_sparse(rg_table_t *t, const rg_batch32_t *in, const rg_outcome32_t *out, int memspace);
 /* Host-side (no device involved): compact outcome rows -> the wide columns, for callers written against rg_outcome_t. `in` and `out` are HOST
  * arrays of rounds*count rows (out->logfx / out->persist rows that carry nothing are zeroed, like rg_submit's). role_epoch: [count], the role
  * epoch of every group BEFORE the batch (rg_group_state_t.role_epoch); updated in place to the epochs after it. Rows flagged
@@ -523,7 +532,7 @@ int rg_timers_expired(rg_table_t *t, int64_t now, uint32_t *out_gid, uint32_t ca
  * the reference drops it (context/RaftRoutine.java:70). out_epoch: [capacity], same memspace as out_gid. */
 int rg_timers_expired_epochs(rg_table_t *t, int64_t now, uint32_t *out_gid, uint32_t *out_epoch, uint32_t capacity, uint32_t *out_count,
                              int memspace);
-/* The same from COMPACT outcome rows (ABI 5; dense batches, as rg_submit32c): row = the rg_out32_t column, persist32 = the rg_persist32_t column of the
+/* The same from COMPACT outcome rows (ABI 5; dense batches only — the rows of rg_submit32c_sparse go through rg_outcome32_unpack and the wide call with their gid list): row = the rg_out32_t column, persist32 = the rg_persist32_t column of the
  * batch just decided, [rounds * groups] each. A compact row names its role epoch only where a conversion happened (rg_persist32_t.role_epoch); the
  * rows before a batch's first conversion are chained from the epoch the group had after the PREVIOUS batch, which the table remembers per group —
  * refreshed by rg_load_state, rg_timers_arm and by every rg_timers_update / rg_timers_update32: the timers must see every batch of the table, in
@@ -571,7 +580,7 @@ int rg_health_read(rg_table_t *t, uint32_t first, uint32_t count, int64_t *reque
  * The table's options and index bases at creation are part of the recording: rg_tick2_launch refuses (-1) when they have changed since.            */
 typedef struct {
     /* in */
-    uint32_t              rounds;           /* 1 .. 64; count is the table's group count (dense) */
+    uint32_t              rounds;           /* 1 .. 64; count is the table's group count (dense). rg_tick2_create_sparse: 1, and every G below reads `capacity` */
     const rg_ev_head_t   *head;             /* [rounds * G] */
     const rg_ev_quad32_t *abcd;             /* [rounds * G] */
     const int32_t        *entry_terms;      /* [entry_capacity] or NULL */
@@ -594,6 +603,28 @@ typedef struct {
 } rg_tick2_io_t;
 typedef struct rg_tick2 rg_tick2_t;
 int rg_tick2_create(rg_table_t *t, const rg_tick2_io_t *io, rg_tick2_t **tick);
+/* THE SPARSE TICK: the same recording for a LIST of groups whose length changes from tick to tick. A node that ticks every ~100 us with 300 ms election timers
+ * has an event for a small share of its groups; the dense tick reads and writes the state, a 24-byte event row, a 16-byte outcome row, a send head and P - 1 send
+ * rows of ALL of them every time. Here only the listed groups are touched (plus 8 bytes of deadline per group of the table for the expiry).
+ *   rows     gid[i] = the group of row i: the first n entries strictly ascending, each below the table's group count (trusted, like every list in device memory);
+ *            n = min(*count, capacity) is READ when the graph runs, like the clocks: refill gid, count, rows and clock, launch, wait. gid and count must be
+ *            device-visible like every other column. capacity (1 .. groups) is what every per-row column is sized for.
+ *   io       rounds must be 1. The per-row columns are indexed by ROW: head, abcd, row, persist32, heartbeat, send_head, ready hold [capacity] rows; in_flight
+ *            and send [(P - 1) * capacity], element (j, row) at j * capacity + row. expired_* are unchanged: they describe the whole table.
+ * One run of the graph: (1) rows 0 .. n - 1 are decided as rg_submit32c_sparse decides them — rows >= n of every output column are NOT TOUCHED; (2) their flags
+ * are folded into the deadlines and the followers' statistics of their groups at now[0], as rg_timers_update / rg_health_update do with that gid list; (3)
+ * send_head[row] / send[j * capacity + row] are what rg_replicate(t, n, gid, heartbeat, in_flight, ..) gives for the row — a leader sends from onTimeout and
+ * acceptCommand only (member/Leader.java:120-140), i.e. only where its group has a row; (4) ready[row] is Leader.isReady of gid[row] at now[0] (rg_ready still has
+ * the whole column); (5) the tickets that fired by now[0] in the WHOLE TABLE, ascending, with their role epochs, marked fired — as in the dense tick. n = 0 is a
+ * legal tick: only (5) happens. The handle is an ordinary rg_tick2_t: rg_tick2_launch / _wait / _destroy, the refusal after a change of options or index bases and
+ * the behaviour of a tick that outlives its table are those of the dense tick. With the list gid[i] = i, n = capacity = groups, every column equals the dense
+ * tick's. Which of the two to record is the caller's choice: it knows its fill. */
+typedef struct {
+    const uint32_t *gid;       /* [capacity] group of row i; the first n entries strictly ascending, each below the table's group count */
+    const uint32_t *count;     /* [1] rows of THIS tick, read when the graph runs; n = min(*count, capacity) */
+    uint32_t        capacity;  /* 1 .. groups: what every per-row column is sized for */
+} rg_tick2_rows_t;
+int rg_tick2_create_sparse(rg_table_t *t, const rg_tick2_io_t *io, const rg_tick2_rows_t *rows, rg_tick2_t **tick);
 int rg_tick2_launch(rg_tick2_t *tick);      /* asynchronous on the table's stream. A launch issued before rg_tick2_wait of the previous one is ORDERED AFTER it
                                                on that stream and does not wait on the host: with every column in device memory a host can queue ticks whose rows
                                                another kernel produces; it reads `row`, the lists and `ready` of the LAST tick only after rg_tick2_wait */

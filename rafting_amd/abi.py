@@ -121,6 +121,10 @@ class CTick2Io(C.Structure):           # rg_tick2_io_t
                 ("expired_capacity", C.c_uint32), ("send_head", C.c_void_p), ("send", C.c_void_p), ("ready", C.c_void_p)]
 
 
+class CTick2Rows(C.Structure):         # rg_tick2_rows_t
+    _fields_ = [("gid", C.c_void_p), ("count", C.c_void_p), ("capacity", C.c_uint32)]
+
+
 _STATE_FIELDS = [
     ("current_term", np.int64, 1),
     ("voted_for", np.int32, 1),

@@ -28,6 +28,8 @@ hipError_t launch_timers_update(const TimerParams &p, hipStream_t s);
 hipError_t launch_tick_fold(const TickFoldParams &p, hipStream_t s);
 hipError_t launch_tick_tail(const TickTailParams &p, int followers, hipStream_t s);
 hipError_t launch_tick(const StepParams &p, const TickTailParams &tp, int followers, hipStream_t s);
+hipError_t launch_tick_sparse(const StepParams &p, const TickTailParams &tp, const uint32_t *rows_now, int followers, hipStream_t s);
+hipError_t launch_tick_expire(const TickFoldParams &p, hipStream_t s);
 hipError_t launch_timers_arm(const TimerParams &p, hipStream_t s);
 hipError_t launch_timers_expired(int64_t *deadline, const Ident *ident, uint32_t groups, int64_t now, const int64_t *now_mem, uint32_t *counts, uint32_t *total,
                                  uint32_t *out_gid, uint32_t *out_epoch, uint32_t capacity, hipStream_t s);
@@ -862,28 +864,37 @@ static int device_visible(rg_table *t, const void *p, const char *what, void **o
     return 0;
 }
 
-int rg_tick2_create(rg_table_t *t, const rg_tick2_io_t *io, rg_tick2_t **tick)
+// rows == nullptr: the dense tick (rg_tick2_create: every group has a row); else the sparse one (rg_tick2_create_sparse: row i belongs to group rows->gid[i], the
+// rows of a run are counted by *rows->count, the per-row columns are sized for rows->capacity)
+static int tick2_create(rg_table_t *t, const rg_tick2_io_t *io, const rg_tick2_rows_t *rows, rg_tick2_t **tick, const char *who)
 {
     if (!t) return -1;
-    if (int rc = compact_ok(t, "rg_tick2_create")) return rc;
-    if (!tick) return fail(t, -1, "rg_tick2_create: tick is NULL");
+    if (int rc = compact_ok(t, who)) return rc;
+    if (!tick) return fail(t, -1, "%s: tick is NULL", who);
     *tick = nullptr;
-    if (!io) return fail(t, -1, "rg_tick2_create: io is NULL");
-    if (io->rounds == 0 || io->rounds > 64) return fail(t, -1, "rg_tick2_create: %u rounds (1 .. 64: one clock per round travels with the tick)", io->rounds);
-    if (!io->head || !io->abcd || !io->now || !io->row || !io->persist32) return fail(t, -1, "rg_tick2_create: head, abcd, now, row and persist32 are required");
-    if (io->entry_capacity && !io->entry_terms) return fail(t, -1, "rg_tick2_create: entry_capacity %llu without entry_terms", (unsigned long long)io->entry_capacity);
-    if (io->expired_gid && (!io->expired_count || io->expired_capacity == 0)) return fail(t, -1, "rg_tick2_create: the expiry step needs expired_count and a capacity");
-    if ((io->send_head == nullptr) != (io->send == nullptr)) return fail(t, -1, "rg_tick2_create: send_head and send come together");
+    if (!io) return fail(t, -1, "%s: io is NULL", who);
+    if (io->rounds == 0 || io->rounds > 64) return fail(t, -1, "%s: %u rounds (1 .. 64: one clock per round travels with the tick)", who, io->rounds);
+    if (!io->head || !io->abcd || !io->now || !io->row || !io->persist32) return fail(t, -1, "%s: head, abcd, now, row and persist32 are required", who);
+    if (io->entry_capacity && !io->entry_terms) return fail(t, -1, "%s: entry_capacity %llu without entry_terms", who, (unsigned long long)io->entry_capacity);
+    if (io->expired_gid && (!io->expired_count || io->expired_capacity == 0)) return fail(t, -1, "%s: the expiry step needs expired_count and a capacity", who);
+    if ((io->send_head == nullptr) != (io->send == nullptr)) return fail(t, -1, "%s: send_head and send come together", who);
+    if (rows) {
+        if (io->rounds != 1) return fail(t, -1, "%s: %u rounds (a list of groups carries exactly one round)", who, io->rounds);
+        if (!rows->gid || !rows->count) return fail(t, -1, "%s: gid and count are required", who);
+        if (rows->capacity == 0 || rows->capacity > t->G) return fail(t, -1, "%s: a capacity of %u rows for %u groups (1 .. groups)", who, rows->capacity, t->G);
+    }
+    const uint32_t R = rows ? rows->capacity : t->G;        // rows the per-row columns are sized for
     rg_batch_t wide{};
-    wide.rounds = io->rounds; wide.count = t->G; wide.head = io->head;
+    wide.rounds = io->rounds; wide.count = R; wide.gid = rows ? rows->gid : nullptr; wide.head = io->head;
     wide.ab = wide.cd = reinterpret_cast<const rg_ev_pair_t *>(io->abcd);
     wide.entry_terms = reinterpret_cast<const int64_t *>(io->entry_terms); wide.entry_count = io->entry_capacity;
     rg_reply_t dummy_r; rg_logfx_t dummy_l; rg_persist_t dummy_p;
     const rg_outcome_t shape{&dummy_r, &dummy_l, &dummy_p};
     if (int rc = check_batch(t, &wide, &shape, false)) return rc;
     if (bind(t)) return -2;
-    void *d_head, *d_abcd, *d_terms, *d_now, *d_hb, *d_fl, *d_row, *d_per, *d_egid, *d_eep, *d_ecnt, *d_sh, *d_ss, *d_ready;
-    if (device_visible(t, io->head, "head", &d_head) || device_visible(t, io->abcd, "abcd", &d_abcd) || device_visible(t, io->entry_terms, "entry_terms", &d_terms) ||
+    void *d_head, *d_abcd, *d_terms, *d_now, *d_hb, *d_fl, *d_row, *d_per, *d_egid, *d_eep, *d_ecnt, *d_sh, *d_ss, *d_ready, *d_gid = nullptr, *d_cnt = nullptr;
+    if ((rows && (device_visible(t, rows->gid, "gid", &d_gid) || device_visible(t, rows->count, "count", &d_cnt))) ||
+        device_visible(t, io->head, "head", &d_head) || device_visible(t, io->abcd, "abcd", &d_abcd) || device_visible(t, io->entry_terms, "entry_terms", &d_terms) ||
         device_visible(t, io->now, "now", &d_now) || device_visible(t, io->heartbeat, "heartbeat", &d_hb) || device_visible(t, io->in_flight, "in_flight", &d_fl) ||
         device_visible(t, io->row, "row", &d_row) || device_visible(t, io->persist32, "persist32", &d_per) || device_visible(t, io->expired_gid, "expired_gid", &d_egid) ||
         device_visible(t, io->expired_epoch, "expired_epoch", &d_eep) || device_visible(t, io->expired_count, "expired_count", &d_ecnt) ||
@@ -892,22 +903,22 @@ int rg_tick2_create(rg_table_t *t, const rg_tick2_io_t *io, rg_tick2_t **tick)
     rg_tick2 *k = new rg_tick2();
     k->t = t;
     k->config_gen = t->config_gen;
-    const uint32_t G = t->G;
-    // the decisions: rg_submit32c on device-visible rows
+    // the decisions: rg_submit32c / rg_submit32c_sparse on device-visible rows
     rg::StepParams sp = step_params(t, &wide);
+    sp.gid = (const uint32_t *)d_gid;
     sp.head = (const rg_ev_head_t *)d_head; sp.abcd32 = (const rg::I32x4 *)d_abcd;
     sp.entry_terms32 = io->entry_capacity ? (const int32_t *)d_terms : nullptr;
     sp.out32 = (rg::I32x4 *)d_row; sp.persist32 = (rg::I32x4 *)d_per;
     // what the batch did to the timers and to the followers' health, from the compact rows where they lie
     rg::TimerParams tp = timer_params(t);
-    tp.rounds = io->rounds; tp.count = G; tp.out32 = (const rg::I32x4 *)d_row; tp.persist32 = (const rg::I32x4 *)d_per; tp.now_mem = (const int64_t *)d_now;
+    tp.rounds = io->rounds; tp.count = R; tp.out32 = (const rg::I32x4 *)d_row; tp.persist32 = (const rg::I32x4 *)d_per; tp.now_mem = (const int64_t *)d_now;
     rg::HealthParams hp = health_params(t);
-    hp.rounds = io->rounds; hp.count = G; hp.head = (const rg_ev_head_t *)d_head; hp.out32 = (const rg::I32x4 *)d_row; hp.now_mem = (const int64_t *)d_now;
+    hp.rounds = io->rounds; hp.count = R; hp.head = (const rg_ev_head_t *)d_head; hp.out32 = (const rg::I32x4 *)d_row; hp.now_mem = (const int64_t *)d_now;
     const int64_t *now_last = (const int64_t *)d_now + (io->rounds - 1);
     rg::HealthParams rp = health_params(t);
     rp.now_mem = now_last;
     rg::ReplicateParams qp{};
-    qp.t = t->dt; qp.count = G; qp.heartbeat = (const uint8_t *)d_hb; qp.in_flight = (const uint16_t *)d_fl; qp.head = (rg_send_head_t *)d_sh; qp.send = (rg_send_t *)d_ss;
+    qp.t = t->dt; qp.count = R; qp.gid = (const uint32_t *)d_gid; qp.heartbeat = (const uint8_t *)d_hb; qp.in_flight = (const uint16_t *)d_fl; qp.head = (rg_send_head_t *)d_sh; qp.send = (rg_send_t *)d_ss;
     hipStream_t s = t->stream;
     // What follows the decisions — what the batch did to the timers and to the followers' health, the list of the tickets that fired, the leaders' sends, the
     // readiness column — is one lane per group with same-group dependencies only, and a single-round tick is launch-bound (~14 us per graph node for ~10 us of
@@ -924,7 +935,11 @@ int rg_tick2_create(rg_table_t *t, const rg_tick2_io_t *io, rg_tick2_t **tick)
     const char *nodes_env = getenv("RG_TICK_NODES");
     const int nodes = (nodes_env && (nodes_env[0] == '2' || nodes_env[0] == '4')) ? nodes_env[0] - '0' : (sp.force_wide != 0 ? 2 : 1);
     hipError_t e = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
-    if (nodes == 1) {
+    if (rows) {
+        // the sparse tick has ONE recording: the rows' workgroups (rg_kernels.hip, tick_sparse_kernel), then — it covers the whole table, whatever the list — the expiry
+        if (e == hipSuccess) e = rg::launch_tick_sparse(sp, tt, (const uint32_t *)d_cnt, (int)t->F, s);
+        if (e == hipSuccess && fp.expire) e = rg::launch_tick_expire(fp, s);
+    } else if (nodes == 1) {
         if (e == hipSuccess) e = rg::launch_tick(sp, tt, (int)t->F, s);
     } else {
         if (e == hipSuccess) e = rg::launch_step(sp, (int)t->F, false, 32, s);
@@ -944,11 +959,22 @@ int rg_tick2_create(rg_table_t *t, const rg_tick2_io_t *io, rg_tick2_t **tick)
     if (e != hipSuccess) {
         (void)hipGetLastError();
         rg_tick2_destroy(k);
-        return fail(t, -2, "rg_tick2_create: %s", hipGetErrorString(e));
+        return fail(t, -2, "%s: %s", who, hipGetErrorString(e));
     }
     t->ticks2.push_back(k);
     *tick = k;
     return 0;
+}
+
+int rg_tick2_create(rg_table_t *t, const rg_tick2_io_t *io, rg_tick2_t **tick)
+{
+    return tick2_create(t, io, nullptr, tick, "rg_tick2_create");
+}
+
+int rg_tick2_create_sparse(rg_table_t *t, const rg_tick2_io_t *io, const rg_tick2_rows_t *rows, rg_tick2_t **tick)
+{
+    if (t && !rows) return fail(t, -1, "rg_tick2_create_sparse: rows is NULL");
+    return tick2_create(t, io, rows, tick, "rg_tick2_create_sparse");
 }
 
 int rg_tick2_launch(rg_tick2_t *k)
@@ -1184,18 +1210,19 @@ static uint32_t host_index_fields(uint32_t kind)
     }
 }
 
-/* compact rows in, compact outcome rows out (ABI 4): see include/raftgpu.h */
-int rg_submit32c(rg_table_t *t, const rg_batch32_t *in, const rg_outcome32_t *out, int memspace)
+/* compact rows in, compact outcome rows out (ABI 4), dense (rg_submit32c) or for a list of groups (rg_submit32c_sparse): see include/raftgpu.h */
+static int submit32c(rg_table_t *t, const rg_batch32_t *in, const rg_outcome32_t *out, int memspace, bool sparse, const char *who)
 {
     if (!t) return -1;
-    if (int rc = compact_ok(t, "rg_submit32c")) return rc;
-    if (!in || !out) return fail(t, -1, "rg_submit32c: NULL batch or outcome");
-    if (!in->head || !in->abcd || !out->row || !out->persist) return fail(t, -1, "rg_submit32c: head, abcd, row and persist are required");
-    if (in->gid) return fail(t, -1, "rg_submit32c: dense batches only (gid must be NULL)");
+    if (int rc = compact_ok(t, who)) return rc;
+    if (!in || !out) return fail(t, -1, "%s: NULL batch or outcome", who);
+    if (!in->head || !in->abcd || !out->row || !out->persist) return fail(t, -1, "%s: head, abcd, row and persist are required", who);
+    if (!sparse && in->gid) return fail(t, -1, "rg_submit32c: dense batches only (gid must be NULL); a list of groups goes through rg_submit32c_sparse");
+    if (sparse && !in->gid) return fail(t, -1, "rg_submit32c_sparse: gid is required (dense batches go through rg_submit32c)");
     const int wides = (out->wide.reply != nullptr) + (out->wide.logfx != nullptr) + (out->wide.persist != nullptr);
-    if (wides != 0 && wides != 3) return fail(t, -1, "rg_submit32c: the overflow columns come as all three or none");
-    rg_batch_t wide{};                              // the same shape rules as every other submission (rounds, count, entry bound)
-    wide.rounds = in->rounds; wide.count = in->count; wide.head = in->head;
+    if (wides != 0 && wides != 3) return fail(t, -1, "%s: the overflow columns come as all three or none", who);
+    rg_batch_t wide{};                              // the same shape rules as every other submission (rounds, count, gid list, entry bound)
+    wide.rounds = in->rounds; wide.count = in->count; wide.gid = in->gid; wide.head = in->head;
     wide.ab = wide.cd = reinterpret_cast<const rg_ev_pair_t *>(in->abcd);      // presence only: check_batch does not read event fields
     wide.entry_terms = reinterpret_cast<const int64_t *>(in->entry_terms); wide.entry_count = in->entry_count;
     rg_reply_t dummy_r; rg_logfx_t dummy_l; rg_persist_t dummy_p;
@@ -1206,13 +1233,13 @@ int rg_submit32c(rg_table_t *t, const rg_batch32_t *in, const rg_outcome32_t *ou
     const size_t rows = (size_t)in->rounds * in->count;
     rg::StepParams p = step_params(t, &wide);
     if (memspace == RG_MEM_DEVICE) {
-        p.head = in->head; p.abcd32 = (const rg::I32x4 *)in->abcd;
+        p.gid = in->gid; p.head = in->head; p.abcd32 = (const rg::I32x4 *)in->abcd;
         p.entry_terms32 = in->entry_count ? in->entry_terms : nullptr;
         p.out32 = (rg::I32x4 *)out->row; p.persist32 = (rg::I32x4 *)out->persist;
         p.reply = out->wide.reply; p.logfx = (I64x2 *)out->wide.logfx; p.persist = out->wide.persist;
-        return launch(t, p, false);
+        return launch(t, p, sparse);
     }
-    if (memspace != RG_MEM_HOST) return fail(t, -1, "rg_submit32c: unknown memspace %d", memspace);
+    if (memspace != RG_MEM_HOST) return fail(t, -1, "%s: unknown memspace %d", who, memspace);
     hipStream_t s = t->stream;
     if (reserve(t, t->st_head, rows * sizeof(rg_ev_head_t)) || reserve(t, t->st_abcd32, rows * sizeof(rg_ev_quad32_t)) ||
         reserve(t, t->st_out32, rows * sizeof(rg_out32_t)) || reserve(t, t->st_persist32, rows * sizeof(rg_persist32_t)))
@@ -1223,6 +1250,11 @@ int rg_submit32c(rg_table_t *t, const rg_batch32_t *in, const rg_outcome32_t *ou
     HIP_TRY(t, hipMemcpyAsync(t->st_head.ptr, in->head, rows * sizeof(rg_ev_head_t), hipMemcpyHostToDevice, s));
     HIP_TRY(t, hipMemcpyAsync(t->st_abcd32.ptr, in->abcd, rows * sizeof(rg_ev_quad32_t), hipMemcpyHostToDevice, s));
     p.head = (const rg_ev_head_t *)t->st_head.ptr; p.abcd32 = (const rg::I32x4 *)t->st_abcd32.ptr;
+    if (sparse) {
+        if (reserve(t, t->st_gid, in->count * sizeof(uint32_t))) return -2;
+        HIP_TRY(t, hipMemcpyAsync(t->st_gid.ptr, in->gid, in->count * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        p.gid = (const uint32_t *)t->st_gid.ptr;
+    }
     if (in->entry_count) {
         if (reserve(t, t->st_terms32, in->entry_count * sizeof(int32_t))) return -2;
         HIP_TRY(t, hipMemcpyAsync(t->st_terms32.ptr, in->entry_terms, in->entry_count * sizeof(int32_t), hipMemcpyHostToDevice, s));
@@ -1236,7 +1268,7 @@ int rg_submit32c(rg_table_t *t, const rg_batch32_t *in, const rg_outcome32_t *ou
         HIP_TRY(t, hipMemsetAsync(t->st_logfx.ptr, 0, rows * sizeof(I64x2), s));
         HIP_TRY(t, hipMemsetAsync(t->st_persist.ptr, 0, rows * sizeof(rg_persist_t), s));
     }
-    if (int rc = launch(t, p, false)) return rc;
+    if (int rc = launch(t, p, sparse)) return rc;
     HIP_TRY(t, hipMemcpyAsync(out->row, t->st_out32.ptr, rows * sizeof(rg_out32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(t, hipMemcpyAsync(out->persist, t->st_persist32.ptr, rows * sizeof(rg_persist32_t), hipMemcpyDeviceToHost, s));
     if (wides) {
@@ -1246,6 +1278,16 @@ int rg_submit32c(rg_table_t *t, const rg_batch32_t *in, const rg_outcome32_t *ou
     }
     HIP_TRY(t, hipStreamSynchronize(s));
     return 0;
+}
+
+int rg_submit32c(rg_table_t *t, const rg_batch32_t *in, const rg_outcome32_t *out, int memspace)
+{
+    return submit32c(t, in, out, memspace, false, "rg_submit32c");
+}
+
+int rg_submit32c_sparse(rg_table_t *t, const rg_batch32_t *in, const rg_outcome32_t *out, int memspace)
+{
+    return submit32c(t, in, out, memspace, true, "rg_submit32c_sparse");
 }
 
 /* host-side: rg_out32_t / rg_persist32_t rows -> the wide columns (no device involved) */

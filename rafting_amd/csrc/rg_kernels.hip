@@ -25,9 +25,11 @@ __device__ __forceinline__ void stream_store(uint4 *dst, const uint4 v)
 // Writes: 48 B head + 32 F B sends per row. The outputs are arrays of structs (what the host reads), so a lane's own struct
 // is not a coalesced unit; every wavefront therefore transposes through LDS and stores WHOLE 1 KiB lines, 16 B per lane:
 // three store instructions for the 64 heads, two per follower for the 64 sends of that follower.
-// (the rows of ONE wavefront: i0 = its first row, st = its own 3 KiB of LDS; replicate_kernel and the fused tail of a recorded tick call it)
+// (the rows of ONE wavefront: i0 = its first row, st = its own 3 KiB of LDS; replicate_kernel and the fused tail of a recorded tick call it.
+//  stride = the rows the follower-major columns `in_flight` and `send` are laid out for: p.count, or — the sparse tick, whose row count changes from
+//  run to run while its columns stay where they are — the capacity they were sized for)
 template <int F>
-__device__ __forceinline__ void replicate_wave(const ReplicateParams &p, uint4 *st, const uint32_t i0, const uint32_t lane)
+__device__ __forceinline__ void replicate_wave(const ReplicateParams &p, uint4 *st, const uint32_t i0, const uint32_t lane, const uint32_t stride)
 {
     const uint32_t i = i0 + lane;
     const bool active = i < p.count;
@@ -48,7 +50,7 @@ __device__ __forceinline__ void replicate_wave(const ReplicateParams &p, uint4 *
     for (int j = 0; j < F; j++) {
         en[j] = I64x2{0, 0}; fl[j] = 0u;
         if (leader & prepared) en[j] = p.t.peer_en[(size_t)j * G + gi];
-        if (leader && p.in_flight) fl[j] = p.in_flight[(size_t)j * p.count + ir];
+        if (leader && p.in_flight) fl[j] = p.in_flight[(size_t)j * stride + ir];
     }
     I64x2 r0{0, 0}, r1{0, 0}, r2{0, 0}, r3{0, 0};
     if (leader & has_log) {
@@ -138,7 +140,7 @@ __device__ __forceinline__ void replicate_wave(const ReplicateParams &p, uint4 *
         const uint4 *sv = reinterpret_cast<const uint4 *>(&sends[j]);
         st[lane * 2 + 0] = sv[0]; st[lane * 2 + 1] = sv[1];
         wave_lds_sync();
-        uint4 *dst = reinterpret_cast<uint4 *>(p.send + (size_t)j * p.count + i0);   // follower-major: element (j, row) at j * count + row
+        uint4 *dst = reinterpret_cast<uint4 *>(p.send + (size_t)j * stride + i0);   // follower-major: element (j, row) at j * stride + row
 #pragma unroll
         for (int k = 0; k < 2; k++) {
             const uint32_t c = (uint32_t)k * 64u + lane;
@@ -153,7 +155,7 @@ __global__ __launch_bounds__(256) void replicate_kernel(const ReplicateParams p)
 {
     __shared__ uint4 stage[4][3 * 64];                // per wavefront: 64 heads (3 x 16 B) or 64 sends (2 x 16 B)
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    replicate_wave<F>(p, stage[wave], blockIdx.x * blockDim.x + wave * 64u, lane);
+    replicate_wave<F>(p, stage[wave], blockIdx.x * blockDim.x + wave * 64u, lane, p.count);
 }
 
 hipError_t launch_replicate(const ReplicateParams &p, int followers, hipStream_t s)
@@ -320,8 +322,9 @@ __global__ __launch_bounds__(256) void timers_emit_kernel(int64_t *deadline, con
 #define RG_AGENT_LOAD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
 #define RG_AGENT_STORE(p, v) __hip_atomic_store((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
 #endif
-// what the batch did to the timer and the follower statistics of group g (timers_update32_kernel + health_update_kernel); returns the deadline it leaves
-__device__ __forceinline__ int64_t fold_group(const TickFoldParams &p, const uint32_t g)
+// what the batch did to the timer and the follower statistics of group g (timers_update32_kernel + health_update_kernel); returns the deadline it leaves.
+// The group's row of round r is row r * p.tp.count + i of the batch's columns: i = g for a dense batch, the row that names g in a list of groups.
+__device__ __forceinline__ int64_t fold_rows_of(const TickFoldParams &p, const uint32_t g, const uint32_t i)
 {
     const uint32_t G = p.tp.count;
     // RaftRoutine.resetTimer for the rows of this group (timers_update32_kernel)
@@ -329,7 +332,7 @@ __device__ __forceinline__ int64_t fold_group(const TickFoldParams &p, const uin
     uint32_t e = p.tp.epoch[g];
     const size_t GG = p.hp.t.groups;
     for (uint32_t r = 0; r < p.tp.rounds; r++) {
-        const size_t row = (size_t)r * G + g;
+        const size_t row = (size_t)r * G + i;
         const uint32_t flags = (uint32_t)p.tp.out32[row].y;
         const int64_t now = p.tp.now_mem[r];
         if (flags & RG_F_PERSIST) e = (uint32_t)p.tp.persist32[row].z;
@@ -352,6 +355,7 @@ __device__ __forceinline__ int64_t fold_group(const TickFoldParams &p, const uin
     p.tp.epoch[g] = e;
     return d;
 }
+__device__ __forceinline__ int64_t fold_group(const TickFoldParams &p, const uint32_t g) { return fold_rows_of(p, g, g); }
 
 // The fired tickets of the whole table, in ascending gid order (see above). EVERY thread of the grid calls it (the barriers); d = the deadline of the lane's
 // group g, `holds` (wave-uniform) = this wavefront has groups at all (lane = group); `part` = at least 136 words of the workgroup's LDS.
@@ -548,7 +552,7 @@ __global__ __launch_bounds__(256) void tick_tail_kernel(const TickTailParams p)
     const uint32_t g = blockIdx.x * 256u + threadIdx.x;
     const bool active = g < p.fp.tp.count;
     const int64_t d = active ? fold_group(p.fp, g) : 0;
-    if (p.qp.head != nullptr) replicate_wave<F>(p.qp, stage[wave], blockIdx.x * 256u + wave * 64u, lane);
+    if (p.qp.head != nullptr) replicate_wave<F>(p.qp, stage[wave], blockIdx.x * 256u + wave * 64u, lane, p.qp.count);
     if (p.ready != nullptr && active) p.ready[g] = ready_of(p.rp, *p.rp.now_mem, p.critical_point, p.cool_down, g);
     if (p.fp.expire) expire_tail(p.fp, d, g, true, active, part);
 }
@@ -582,7 +586,7 @@ __global__ __launch_bounds__(2 * BLOCK) __attribute__((amdgpu_waves_per_eu(WAVES
     if (holds) {
         if (active) d = fold_group(tp.fp, g);
     } else {
-        if (tp.qp.head != nullptr) replicate_wave<F>(tp.qp, stage, blockIdx.x * BLOCK, lane);
+        if (tp.qp.head != nullptr) replicate_wave<F>(tp.qp, stage, blockIdx.x * BLOCK, lane, tp.qp.count);
     }
     __syncthreads();
     if (!holds && tp.ready != nullptr && in_table) tp.ready[g] = ready_of(tp.rp, *tp.rp.now_mem, tp.critical_point, tp.cool_down, g);
@@ -601,6 +605,76 @@ hipError_t launch_tick(const StepParams &p, const TickTailParams &tp, int follow
 #undef RG_TICK_CASE
     default: return hipErrorInvalidValue;
     }
+    return hipGetLastError();
+}
+// ---- the SPARSE recorded tick (rg_tick2_create_sparse): the same for a LIST of groups whose length changes from run to run --------------------------------
+// Most groups of a 100-us tick have no event, and tick_kernel reads and writes all of them all the same. Here a workgroup is 64 ROWS: row i of every per-row
+// column belongs to group gid[i], the columns are sized for p0.count = the tick's capacity, and the rows of THIS run — n = min(*rows_now, capacity) — are read
+// from device-visible memory when the graph runs, like the clocks. Workgroups past the last row leave at once; the others decide their rows with the
+// list-of-groups instantiations of the step bodies on a LOCAL copy of the parameters whose count is n (so the lanes past n shadow row n - 1 and store nothing
+// beyond it) and then do tick_kernel's tail for them: fold, send rows, readiness — through gid. A table built with RG_FORCE_WIDE=1 leaves the 32-bit body at its
+// state load, as every compact launch of such a table does. The expiry is not here: it covers the whole table, whatever the list — tick_expire_kernel, next node.
+template <int F, int WAVES>
+__global__ __launch_bounds__(2 * BLOCK) __attribute__((amdgpu_waves_per_eu(WAVES, 8))) void tick_sparse_kernel(const StepParams p0, const TickTailParams tp, const uint32_t *rows_now)
+{
+    __shared__ alignas(16) unsigned char smem[SplitLds<F, true, 2>::BYTES];
+    static_assert(SplitLds<F, true, 2>::BYTES >= 3 * 64 * 16, "the tail's staging rows reuse the step's LDS");
+    const uint32_t given = *rows_now, n = given < p0.count ? given : p0.count;
+    if (blockIdx.x * (uint32_t)BLOCK >= n) return;           // (workgroup-uniform: nobody is left waiting at a barrier; n = 0 is a tick without rows)
+    StepParams p = p0;
+    p.count = n;
+    if (!narrow_body<F, true, true, 1, 1>(p, smem)) {
+        if (threadIdx.x == 0) { RG_NOTE_FALLBACK(); atomicAdd(p.wide_bodies, 1ull); }
+        lds_barrier();
+        split_body<F, true, true, true>(p, smem);
+    }
+    __syncthreads();                                         // every store of this workgroup has landed; its LDS is free
+    uint4 *stage = reinterpret_cast<uint4 *>(smem);
+    // as in tick_kernel: the first wavefront folds its rows' flags into the timers and the statistics of THEIR groups while the second plans those groups' sends
+    // (neither reads what the other writes); isReady needs both, so it comes after a meeting
+    const uint32_t lane = threadIdx.x & 63u;
+    const bool holds = __builtin_amdgcn_readfirstlane(threadIdx.x) < (uint32_t)BLOCK;
+    const uint32_t row = blockIdx.x * BLOCK + lane;
+    const bool in_list = row < n;
+    const uint32_t g = p.gid[in_list ? row : n - 1u];
+    if (holds) {
+        if (in_list) fold_rows_of(tp.fp, g, row);
+    } else if (tp.qp.head != nullptr) {
+        ReplicateParams qp = tp.qp;
+        qp.count = n;                                        // (the rows of this run; in_flight / send keep the capacity's layout: the stride)
+        replicate_wave<F>(qp, stage, blockIdx.x * BLOCK, lane, p0.count);
+    }
+    __syncthreads();
+    if (!holds && tp.ready != nullptr && in_list) tp.ready[row] = ready_of(tp.rp, *tp.rp.now_mem, tp.critical_point, tp.cool_down, g);
+}
+// the fired tickets of the whole table at now[0], one lane per group: the sparse tick's second node (expire_tail as the dense kernels call it)
+__global__ __launch_bounds__(256) void tick_expire_kernel(const TickFoldParams p)
+{
+    __shared__ uint32_t part[136];
+    const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+    const bool active = g < p.tp.groups;
+    const int64_t d = active ? p.tp.deadline[g] : 0;
+    expire_tail(p, d, g, true, active, part);
+}
+// p.count = the capacity (1 .. groups): what the per-row columns are sized for, and the grid
+hipError_t launch_tick_sparse(const StepParams &p, const TickTailParams &tp, const uint32_t *rows_now, int followers, hipStream_t s)
+{
+    const uint32_t blocks = (p.count + BLOCK - 1) / BLOCK;
+    if (blocks == 0 || p.count >= (1u << 28) || p.out32 == nullptr || p.gid == nullptr || rows_now == nullptr || p.rounds != 1u) return hipErrorInvalidValue;
+    const bool many = blocks > 1024u;
+    const dim3 grid(blocks), wg(2 * BLOCK);
+    switch (followers) {
+#define RG_TICK_CASE(F_) case F_: if (many) hipLaunchKernelGGL((tick_sparse_kernel<F_, 4>), grid, wg, 0, s, p, tp, rows_now); else hipLaunchKernelGGL((tick_sparse_kernel<F_, 1>), grid, wg, 0, s, p, tp, rows_now); break;
+    RG_TICK_CASE(1) RG_TICK_CASE(2) RG_TICK_CASE(3) RG_TICK_CASE(4) RG_TICK_CASE(5) RG_TICK_CASE(6)
+#undef RG_TICK_CASE
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+hipError_t launch_tick_expire(const TickFoldParams &p, hipStream_t s)
+{
+    if (p.tp.groups == 0) return hipSuccess;
+    hipLaunchKernelGGL(tick_expire_kernel, dim3((p.tp.groups + 255) / 256), dim3(256), 0, s, p);
     return hipGetLastError();
 }
 hipError_t launch_tick_tail(const TickTailParams &p, int followers, hipStream_t s)

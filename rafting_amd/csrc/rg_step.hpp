@@ -1231,8 +1231,17 @@ static hipError_t launch_compact(const StepParams &p, bool sparse, hipStream_t s
     if (p.count >= (1u << 28)) return hipErrorInvalidValue;       // the I/O wavefront addresses a row as scalar base + 32-bit lane offset
     const bool many = blocks > 1024u;                    // more than one workgroup per pair of SIMDs on a 256-CU part
     const dim3 grid(blocks), wg(2 * BLOCK);
-    if (p.out32 != nullptr) {                            // compact outcome rows (rg_submit32c): dense batches only
-        if (sparse) return hipErrorInvalidValue;
+    if (p.out32 != nullptr && sparse) {                  // compact outcome rows for a list of groups (rg_submit32c_sparse): row i of every column belongs to group gid[i]
+        if (p.force_wide != 0) {
+            if (many) hipLaunchKernelGGL((step32_wide_kernel<F, true, 4, true>), grid, wg, 0, s, p);
+            else      hipLaunchKernelGGL((step32_wide_kernel<F, true, 1, true>), grid, wg, 0, s, p);
+        } else {
+            if (many) hipLaunchKernelGGL((step32_kernel<F, true, 4, true>), grid, wg, 0, s, p);
+            else      hipLaunchKernelGGL((step32_kernel<F, true, 1, true>), grid, wg, 0, s, p);
+        }
+        return hipGetLastError();
+    }
+    if (p.out32 != nullptr) {                            // compact outcome rows (rg_submit32c)
         if (p.force_wide != 0) {
             if (many) hipLaunchKernelGGL((step32_wide_kernel<F, false, 4, true>), grid, wg, 0, s, p);
             else      hipLaunchKernelGGL((step32_wide_kernel<F, false, 1, true>), grid, wg, 0, s, p);

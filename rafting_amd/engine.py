@@ -31,7 +31,7 @@ def exported_symbols():
     """Every entry point include/raftgpu.h declares."""
     return [
         "rg_abi_version", "rg_table_create", "rg_table_destroy", "rg_last_error", "rg_table_groups",
-        "rg_table_cluster", "rg_table_option", "rg_load_state", "rg_read_state", "rg_submit", "rg_submit32", "rg_submit32c", "rg_outcome32_unpack", "rg_outcome32_unpack_rel", "rg_index_base_set", "rg_index_base_get", "rg_index_base_advance", "rg_index_base_advance32", "rg_batch32_pack_rel", "rg_batch32_pack", "rg_submit_async", "rg_submit_async_packed", "rg_submit_wait", "rg_tick_create", "rg_tick_launch", "rg_tick_wait", "rg_tick_destroy", "rg_tick2_create", "rg_tick2_launch", "rg_tick2_wait", "rg_tick2_destroy", "rg_timers_update32", "rg_health_update32", "rg_sync", "rg_step_kernel", "rg_host_alloc", "rg_host_free", "rg_dev_alloc",
+        "rg_table_cluster", "rg_table_option", "rg_load_state", "rg_read_state", "rg_submit", "rg_submit32", "rg_submit32c", "rg_submit32c_sparse", "rg_outcome32_unpack", "rg_outcome32_unpack_rel", "rg_index_base_set", "rg_index_base_get", "rg_index_base_advance", "rg_index_base_advance32", "rg_batch32_pack_rel", "rg_batch32_pack", "rg_submit_async", "rg_submit_async_packed", "rg_submit_wait", "rg_tick_create", "rg_tick_launch", "rg_tick_wait", "rg_tick_destroy", "rg_tick2_create", "rg_tick2_create_sparse", "rg_tick2_launch", "rg_tick2_wait", "rg_tick2_destroy", "rg_timers_update32", "rg_health_update32", "rg_sync", "rg_step_kernel", "rg_host_alloc", "rg_host_free", "rg_dev_alloc",
         "rg_dev_free", "rg_copy_to_device", "rg_copy_to_host", "rg_stream", "rg_replicate", "rg_timers_configure", "rg_timers_update",
         "rg_timers_expired", "rg_timers_expired_epochs", "rg_timers_arm", "rg_timers_read", "rg_health_update", "rg_health_failure", "rg_ready", "rg_health_read",
         "rg_timing_enable",
@@ -105,6 +105,7 @@ def lib():
                         return _Missing()
             real, L = L, _Tolerant(L)
         L.rg_submit32c.argtypes = [vp, C.POINTER(abi.CBatch32), C.POINTER(abi.COutcome32), i32]
+        L.rg_submit32c_sparse.argtypes = [vp, C.POINTER(abi.CBatch32), C.POINTER(abi.COutcome32), i32]
         L.rg_outcome32_unpack.argtypes = [C.POINTER(abi.COutcome32), u32, u32, vp, C.POINTER(abi.COutcome)]
         L.rg_outcome32_unpack_rel.argtypes = [C.POINTER(abi.COutcome32), u32, u32, vp, vp, C.POINTER(abi.COutcome)]
         L.rg_index_base_set.argtypes = [vp, u32, u32, vp]
@@ -124,6 +125,7 @@ def lib():
         L.rg_tick_wait.argtypes = [vp]
         L.rg_tick_destroy.argtypes = [vp]
         L.rg_tick2_create.argtypes = [vp, C.POINTER(abi.CTick2Io), C.POINTER(vp)]
+        L.rg_tick2_create_sparse.argtypes = [vp, C.POINTER(abi.CTick2Io), C.POINTER(abi.CTick2Rows), C.POINTER(vp)]
         L.rg_tick2_launch.argtypes = [vp]
         L.rg_tick2_wait.argtypes = [vp]
         L.rg_tick2_destroy.argtypes = [vp]
@@ -343,11 +345,16 @@ class Tick2:
     """The device-resident tick (rg_tick2_create): compact rows in, compact outcome rows out, the batch folded into the timers and the followers' health,
     the fired tickets listed, the leaders' send table and the readiness gate — ONE HIP graph, replayed with launch() / wait(). Every column lives in
     page-locked host memory here (the device reads and writes it over the link) so that a test can fill and read it with numpy; a deployment puts what
-    only the device consumes into HBM (rg_dev_alloc).  refill(batch, now[, heartbeat, in_flight]) writes the next tick's rows and clocks."""
+    only the device consumes into HBM (rg_dev_alloc).  refill(batch, now[, heartbeat, in_flight]) writes the next tick's rows and clocks.
+    sparse_cap=N records the SPARSE tick (rg_tick2_create_sparse): refill takes a batch with a gid list of n <= N rows, every per-row column is indexed by
+    row (heartbeat [n]; in_flight follower-major for those n rows), outcome32() / sends() / readiness() return the n rows of the last refill; the expired
+    list still describes the whole table. The row count always lives in page-locked host memory."""
 
-    def __init__(self, table, rounds, entry_cap=0, expired_cap=None, send=True, ready=True, critical_point=0, cool_down_ms=0, device_resident=False):
-        G, F = table.groups, table.cluster - 1
-        self.table, self.rounds, self.G, self.F = table, rounds, G, F
+    def __init__(self, table, rounds, entry_cap=0, expired_cap=None, send=True, ready=True, critical_point=0, cool_down_ms=0, device_resident=False, sparse_cap=None):
+        F = table.cluster - 1
+        G = table.groups if sparse_cap is None else int(sparse_cap)      # (G: the rows every per-row column is sized for)
+        self.table, self.rounds, self.G, self.F, self.sparse = table, rounds, G, F, sparse_cap is not None
+        self.n = G                                                        # rows of the last refill
         rows = rounds * G
         self._pins = []
         self._devs = []
@@ -369,7 +376,7 @@ class Tick2:
         self.now = col(np.int64, rounds)
         self.heartbeat, self.in_flight = big(np.uint8, G), big(np.uint16, F * G)      # (read by every lane of the send kernel: over the link they cost it tens of microseconds)
         self.row, self.persist32 = big(abi.OUT32_DT, rows), big(abi.PERSIST32_DT, rows)
-        cap = G if expired_cap is None else expired_cap
+        cap = table.groups if expired_cap is None else expired_cap
         self.expired_cap = cap
         self.expired_gid, self.expired_epoch, self.expired_count = (col(np.uint32, cap), col(np.uint32, cap), col(np.uint32, 1)) if cap else (None, None, None)
         self.send_head, self.send = (big(abi.SEND_HEAD_DT, G), big(abi.SEND_DT, F * G)) if send else (None, None)
@@ -384,21 +391,36 @@ class Tick2:
         io.send_head, io.send, io.ready = addr(self.send_head), addr(self.send), addr(self.ready)
         self.io = io
         h = C.c_void_p()
-        table._check(lib().rg_tick2_create(table._h, C.byref(io), C.byref(h)))
+        if self.sparse:
+            self.gid, self.count = big(np.uint32, G), col(np.uint32, 1)
+            rw = abi.CTick2Rows()
+            rw.gid, rw.count, rw.capacity = addr(self.gid), addr(self.count), G
+            self.rows = rw
+            table._check(lib().rg_tick2_create_sparse(table._h, C.byref(io), C.byref(rw), C.byref(h)))
+        else:
+            table._check(lib().rg_tick2_create(table._h, C.byref(io), C.byref(h)))
         self._h = h
 
-    def _put(self, dst, src):
+    def _put(self, dst, src, at=0):
+        if len(src) == 0:
+            return
         if isinstance(dst, DeviceBuffer):
             a = np.ascontiguousarray(src)
-            self.table._check(lib().rg_copy_to_device(self.table._h, dst.ptr, a.ctypes.data, a.nbytes))
+            self.table._check(lib().rg_copy_to_device(self.table._h, dst.ptr + at * a.dtype.itemsize, a.ctypes.data, a.nbytes))
         else:
-            dst[: len(src)] = src
+            dst[at: at + len(src)] = src
 
     def _get(self, src, dtype, n):
         return src.to_host(dtype, n) if isinstance(src, DeviceBuffer) else np.array(src[:n], copy=True)
 
     def refill(self, batch, now, heartbeat=None, in_flight=None, index_base=None):
+        if self.sparse and batch.count == 0:               # a tick without rows: only the clock and the count travel
+            self.now[:] = np.asarray(now, dtype=np.int64)
+            self.count[0] = self.n = 0
+            return
         b32 = batch if isinstance(batch, abi.Batch32) else pack32(batch, index_base)
+        if self.sparse:
+            return self._refill_rows(b32, now, heartbeat, in_flight)
         assert (b32.rounds, b32.count) == (self.rounds, self.G) and b32.gid is None and b32.entry_count <= self.io.entry_capacity
         self._put(self.head, b32.head)
         self._put(self.abcd, b32.abcd)
@@ -410,6 +432,23 @@ class Tick2:
         if in_flight is not None or not isinstance(self.in_flight, DeviceBuffer):
             self._put(self.in_flight, np.zeros(self.F * self.G, np.uint16) if in_flight is None else np.ascontiguousarray(np.asarray(in_flight, dtype=np.uint16).reshape(-1)))
 
+    def _refill_rows(self, b32, now, heartbeat, in_flight):
+        """the sparse tick: n = b32.count rows for the groups b32.gid names; rows n .. capacity - 1 of every column keep what they held"""
+        n = b32.count
+        assert b32.rounds == 1 and b32.gid is not None and len(b32.gid) == n <= self.G and b32.entry_count <= self.io.entry_capacity
+        self._put(self.gid, np.ascontiguousarray(b32.gid, dtype=np.uint32))
+        self._put(self.head, b32.head[:n])
+        self._put(self.abcd, b32.abcd[:n])
+        if b32.entry_count:
+            self._put(self.entry_terms, b32.entry_terms[: b32.entry_count])
+        self.now[:] = np.asarray(now, dtype=np.int64)
+        self._put(self.heartbeat, np.zeros(n, np.uint8) if heartbeat is None else np.ascontiguousarray(heartbeat, dtype=np.uint8).reshape(n))
+        fl = np.zeros((self.F, n), np.uint16) if in_flight is None else np.ascontiguousarray(np.asarray(in_flight, dtype=np.uint16).reshape(self.F, n))
+        for j in range(self.F):                            # element (j, row) at j * capacity + row
+            self._put(self.in_flight, fl[j], at=j * self.G)
+        self.count[0] = n
+        self.n = n
+
     def launch(self):
         self.table._check(lib().rg_tick2_launch(self._h))
 
@@ -417,7 +456,7 @@ class Tick2:
         self.table._check(lib().rg_tick2_wait(self._h))
 
     def outcome32(self):
-        rows = self.rounds * self.G
+        rows = self.rounds * self.n
         out = abi.Outcome32(rows, wide=False)
         out.row, out.persist = self._get(self.row, abi.OUT32_DT, rows), self._get(self.persist32, abi.PERSIST32_DT, rows)
         return out
@@ -429,10 +468,10 @@ class Tick2:
         return np.array(self.expired_gid[:k]), np.array(self.expired_epoch[:k]), n
 
     def sends(self):
-        return self._get(self.send_head, abi.SEND_HEAD_DT, self.G), self._get(self.send, abi.SEND_DT, self.F * self.G).reshape(self.F, self.G).T.copy()
+        return self._get(self.send_head, abi.SEND_HEAD_DT, self.n), self._get(self.send, abi.SEND_DT, self.F * self.G).reshape(self.F, self.G)[:, : self.n].T.copy()
 
     def readiness(self):
-        return self._get(self.ready, np.uint8, self.G)
+        return self._get(self.ready, np.uint8, self.n)
 
     def close(self):
         if self._h:
@@ -662,6 +701,15 @@ class Table:
         out32 = abi.Outcome32(b32.rounds * b32.count, fill, wide=wide) if out32 is None else out32
         b, o = b32.as_struct(), out32.as_struct()
         self._check(lib().rg_submit32c(self._h, C.byref(b), C.byref(o), abi.MEM_HOST))
+        return out32
+
+    def submit32c_sparse(self, batch, out32=None, fill=0, wide=True, index_base=None):
+        """rg_submit32c for a LIST of groups (rg_submit32c_sparse, RG_MEM_HOST): `batch` carries a gid list; row i of the abi.Outcome32 belongs to group gid[i].
+        index_base (abi.Batch only): the bases of every group of the table, to pack the rows against"""
+        b32 = batch if isinstance(batch, abi.Batch32) else pack32(batch, index_base)
+        out32 = abi.Outcome32(b32.rounds * b32.count, fill, wide=wide) if out32 is None else out32
+        b, o = b32.as_struct(), out32.as_struct()
+        self._check(lib().rg_submit32c_sparse(self._h, C.byref(b), C.byref(o), abi.MEM_HOST))
         return out32
 
     def submit32c_unpacked(self, batch, role_epoch_before, fill=0):
