@@ -62,7 +62,8 @@ extern "C" {
                                      4: compact OUTCOME rows (rg_out32_t, rg_submit32c, rg_outcome32_unpack, RG_F_WIDE_VALUES); rg_table_option; the index base of the compact formats (rg_index_base_set)
                                      5: the device-resident tick on compact outcome rows: rg_timers_update32, rg_health_update32, rg_tick2_*; clusters of up to 15 nodes
                                      6: automatic index bases: RG_OPT_AUTO_INDEX_BASE, rg_index_base_advance / rg_index_base_advance32
-                                        (still 6, new symbols only — nothing that existed changed: rg_submit32c_sparse, rg_tick2_rows_t, rg_tick2_create_sparse) */
+                                        (still 6, new symbols only — nothing that existed changed: rg_submit32c_sparse, rg_tick2_rows_t, rg_tick2_create_sparse;
+                                         then rg_submit32c_sparse_rounds, rg_tick2_rounds_t, rg_tick2_create_sparse_rounds: a list of groups with R rounds) */
 #define RG_MIN_CLUSTER      2     /* P: cluster size incl. self (RaftCluster.size()) */
 #define RG_MAX_CLUSTER      15    /* (ABI 5; the slot field of a row header is 4 bits. Leadership.majorIndices sorts any number of followers, member/Leadership.java:116-130.)
                                      Clusters of up to RG_MAX_COMPACT_CLUSTER nodes have every kernel; larger ones are decided by the wide-row kernels only:
@@ -403,7 +404,7 @@ int64_t rg_batch32_pack(const rg_batch_t *in, rg_ev_head_t *head, rg_ev_quad32_t
  *       STARTED with; a = 0 moves nothing). All rows and outcome rows of a launch stay relative to the bases the launch started with; the new bases apply
  *       from the next launch (the next replay, for a recorded tick).
  * It depends on the rows only, never on outcomes: a host works out the bases of batch k + 1 before batch k is decided (rg_index_base_advance* below), which
- * is what two batches in flight need. Every submission path applies it — rg_submit / rg_submit_async (wide rows: absolute a), rg_submit32, rg_submit32c, rg_submit32c_sparse,
+ * is what two batches in flight need. Every submission path applies it — rg_submit / rg_submit_async (wide rows: absolute a), rg_submit32, rg_submit32c, rg_submit32c_sparse(_rounds),
  * rg_submit_async_packed, rg_tick_*, rg_tick2_* (dense and sparse), host and device memory alike. Nothing else moves a base: rg_load_state leaves the bases alone, rg_index_base_set
  * still sets them and the automatic moves go on from there, and the rule never lowers one. Decisions never depend on it (every reply, effect and persist row
  * is the one without it); it only decides which body decides a workgroup, and what rg_index_base_get reports. A group whose state falls outside
@@ -412,9 +413,9 @@ int64_t rg_batch32_pack(const rg_batch_t *in, rg_ev_head_t *head, rg_ev_quad32_t
 int rg_index_base_set(rg_table_t *t, uint32_t first, uint32_t count, const int64_t *base);
 int rg_index_base_get(rg_table_t *t, uint32_t first, uint32_t count, int64_t *base);
 /* Host-side (no device involved): the rule above applied IN PLACE to a caller's mirror index_base[groups] for one batch, every round, dense (count == groups)
- * or sparse (rounds == 1, gid < groups). rg_index_base_advance takes wide rows (absolute a); rg_index_base_advance32 compact rows, whose a is relative to the
+ * or a list of groups (gid < groups, any number of rounds: row (r, i) at r * count + i belongs to group gid[i]). rg_index_base_advance takes wide rows (absolute a); rg_index_base_advance32 compact rows, whose a is relative to the
  * array AS IT IS ON ENTRY. window: as RG_OPT_AUTO_INDEX_BASE, 1 <= W < 2^30. Returns 0; -1 a missing column (head, ab / abcd, index_base) or a window out of
- * range; -2 a batch of another shape (count, gid, rounds). */
+ * range; -2 a batch of another shape (count, gid). */
 int rg_index_base_advance(const rg_batch_t *in, int32_t window, uint32_t groups, int64_t *index_base);
 int rg_index_base_advance32(const rg_batch32_t *in, int32_t window, uint32_t groups, int64_t *index_base);
 /* rg_batch32_pack with bases: index_base[g] for every group of the table (NULL: all 0); -3 also when an index lies at or below its group's base */
@@ -453,6 +454,18 @@ int rg_submit32c(rg_table_t *t, const rg_batch32_t *in, const rg_outcome32_t *ou
  * rg_outcome32_unpack(_rel) with the role epochs / index bases of the listed groups gathered per row — and the table state are those of rg_submit32 on the
  * same batch. */
 int rg_submit32c_sparse(rg_table_t *t, const rg_batch32_t *in, const rg_outcome32_t *out, int memspace);
+/* rg_submit32c_sparse for R >= 1 ROUNDS, one launch: what a busy tick queues for a few groups — an AppendEntries, its ack, a client append (the reference's event
+ * loop drains whatever is queued per context, support/EventLoopGroup.java:32-46). Round r of every column, in and out, occupies rows [r * count, (r + 1) * count);
+ * row i of EVERY round belongs to group gid[i]; a group with fewer events than R carries RG_EV_NONE rows. in->rounds is bounded as for rg_submit32c, a round holds
+ * fewer than 2^28 rows, RG_MEM_HOST validates the list as rg_submit does and stages rounds * count rows; everything else as rg_submit32c_sparse. The contract:
+ *   - outcome row (r, i) equals row (r, gid[i]) of rg_submit32c on the dense rounds x groups batch that holds the same rows at the listed groups and RG_EV_NONE
+ *     everywhere else (log_from under its marks, persist under RG_F_PERSIST, as everywhere), and the table state afterwards is the same; groups outside the list are
+ *     untouched bit for bit. That covers a group that answers RG_NEED_HOST in round r — RG_SKIPPED_AFTER_NEED_HOST in its later rounds of the launch, its state as
+ *     it was —, a workgroup that leaves the 32-bit domain in the middle of the launch and starts again on the 64-bit body, and RG_FORCE_WIDE=1;
+ *   - index bases: the rows of every round, in and out, are relative to the bases the launch STARTED with; every LOG_FLUSH row of any round moves its group's base
+ *     for the next launch under RG_OPT_AUTO_INDEX_BASE (rg_index_base_advance / rg_index_base_advance32 take the same shape);
+ *   - with rounds == 1 the rows are rg_submit32c_sparse's. */
+int rg_submit32c_sparse_rounds(rg_table_t *t, const rg_batch32_t *in, const rg_outcome32_t *out, int memspace);
 /* Host-side (no device involved): compact outcome rows -> the wide columns, for callers written against rg_outcome_t. `in` and `out` are HOST
  * arrays of rounds*count rows (out->logfx / out->persist rows that carry nothing are zeroed, like rg_submit's). role_epoch: [count], the role
  * epoch of every group BEFORE the batch (rg_group_state_t.role_epoch); updated in place to the epochs after it. Rows flagged
@@ -580,7 +593,7 @@ int rg_health_read(rg_table_t *t, uint32_t first, uint32_t count, int64_t *reque
  * The table's options and index bases at creation are part of the recording: rg_tick2_launch refuses (-1) when they have changed since.            */
 typedef struct {
     /* in */
-    uint32_t              rounds;           /* 1 .. 64; count is the table's group count (dense). rg_tick2_create_sparse: 1, and every G below reads `capacity` */
+    uint32_t              rounds;           /* 1 .. 64; count is the table's group count (dense). rg_tick2_create_sparse: 1, and every G below reads `capacity`; rg_tick2_create_sparse_rounds: the greatest depth */
     const rg_ev_head_t   *head;             /* [rounds * G] */
     const rg_ev_quad32_t *abcd;             /* [rounds * G] */
     const int32_t        *entry_terms;      /* [entry_capacity] or NULL */
@@ -625,6 +638,28 @@ typedef struct {
     uint32_t        capacity;  /* 1 .. groups: what every per-row column is sized for */
 } rg_tick2_rows_t;
 int rg_tick2_create_sparse(rg_table_t *t, const rg_tick2_io_t *io, const rg_tick2_rows_t *rows, rg_tick2_t **tick);
+/* THE SPARSE TICK WITH A DEPTH: the same recording for a list of groups some of which have two or three events queued. Both the row count AND the depth of a run are
+ * read when the graph runs: refill gid, count, rounds, the rows of rounds 0 .. R - 1 and their clocks, launch, wait — one launch where the one-round sparse tick
+ * needs R (what that is worth in time: DESIGN.md section 6).
+ *   io       rounds is the GREATEST depth (1 .. 64). head, abcd, row and persist32 are [io->rounds][capacity]: row i of round r lies at r * capacity + i — the stride
+ *            is the capacity, whatever n and R are in a run. now holds io->rounds clocks. heartbeat, in_flight, send_head, send and ready stay per row
+ *            ([capacity], [(P - 1) * capacity]); expired_* describe the whole table.
+ *   rows     gid, count, capacity as rg_tick2_rows_t; rounds: [1], device-visible, R = clamp(*rounds, 1, io->rounds); NULL: every run has io->rounds rounds.
+ * One run: (1) rows 0 .. n - 1 of rounds 0 .. R - 1 are decided as rg_submit32c_sparse_rounds decides them; (2) their flags are folded into the deadlines and the
+ * followers' statistics of their groups, round by round at now[r] — what rg_timers_update / rg_health_update give with that gid list and R rounds; (3) send_head[row] /
+ * send[j * capacity + row] are rg_replicate's answer for the row after round R - 1; (4) ready[row] is Leader.isReady at now[R - 1]; (5) the fired tickets of the whole
+ * table are taken at now[R - 1]. Rows >= n of any round and rounds >= R are NOT TOUCHED in any output column. n = 0 is a legal tick: expiry only, at now[R - 1].
+ * With rounds == NULL or *rounds == io->rounds, the list gid[i] = i and n = capacity = groups, every column equals the dense io->rounds-round tick's; with
+ * io->rounds == 1 every column equals rg_tick2_create_sparse's. The handle is an ordinary rg_tick2_t: launch / wait / destroy, the refusal after a change of options or
+ * index bases and a tick that outlives its table are all as above. Refused before anything is recorded, each with a message: a missing gid / count, a capacity of 0 or
+ * above the group count, io->rounds outside 1 .. 64, a column or a `rounds` that is not device-visible, a cluster above RG_MAX_COMPACT_CLUSTER. */
+typedef struct {
+    const uint32_t *gid;       /* [capacity] as rg_tick2_rows_t */
+    const uint32_t *count;     /* [1] rows of THIS tick, n = min(*count, capacity), read when the graph runs */
+    const uint32_t *rounds;    /* [1] depth of THIS tick, R = clamp(*rounds, 1, io->rounds), read when the graph runs; NULL: always io->rounds */
+    uint32_t        capacity;  /* 1 .. groups */
+} rg_tick2_rounds_t;
+int rg_tick2_create_sparse_rounds(rg_table_t *t, const rg_tick2_io_t *io, const rg_tick2_rounds_t *rows, rg_tick2_t **tick);
 int rg_tick2_launch(rg_tick2_t *tick);      /* asynchronous on the table's stream. A launch issued before rg_tick2_wait of the previous one is ORDERED AFTER it
                                                on that stream and does not wait on the host: with every column in device memory a host can queue ticks whose rows
                                                another kernel produces; it reads `row`, the lists and `ready` of the LAST tick only after rg_tick2_wait */

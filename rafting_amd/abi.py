@@ -125,6 +125,10 @@ class CTick2Rows(C.Structure):         # rg_tick2_rows_t
     _fields_ = [("gid", C.c_void_p), ("count", C.c_void_p), ("capacity", C.c_uint32)]
 
 
+class CTick2Rounds(C.Structure):       # rg_tick2_rounds_t
+    _fields_ = [("gid", C.c_void_p), ("count", C.c_void_p), ("rounds", C.c_void_p), ("capacity", C.c_uint32)]
+
+
 _STATE_FIELDS = [
     ("current_term", np.int64, 1),
     ("voted_for", np.int32, 1),

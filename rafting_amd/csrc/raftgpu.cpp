@@ -489,7 +489,8 @@ static int compact_ok(rg_table *t, const char *who)
     return 0;
 }
 
-static int check_batch(rg_table *t, const rg_batch_t *in, const rg_outcome_t *out, bool host_memory)
+// list_rounds: the caller takes a list of groups with any number of rounds (rg_submit32c_sparse_rounds, rg_tick2_create_sparse_rounds)
+static int check_batch(rg_table *t, const rg_batch_t *in, const rg_outcome_t *out, bool host_memory, bool list_rounds = false)
 {
     if (!in || !out) return fail(t, -1, "rg_submit: NULL batch or outcome");
     if (!in->head || !in->ab || !in->cd || !out->reply || !out->logfx || !out->persist)
@@ -497,7 +498,7 @@ static int check_batch(rg_table *t, const rg_batch_t *in, const rg_outcome_t *ou
     if (in->rounds == 0) return fail(t, -1, "rg_submit: rounds must be >= 1");
     const bool sparse = in->gid != nullptr;
     if (sparse) {
-        if (in->rounds != 1) return fail(t, -1, "rg_submit: sparse batches carry exactly one round");
+        if (in->rounds != 1 && !list_rounds) return fail(t, -1, "rg_submit: sparse batches carry exactly one round");
         if (in->count > t->G) return fail(t, -1, "rg_submit: %u rows for %u groups", in->count, t->G);
     } else if (in->count != t->G) {
         return fail(t, -1, "rg_submit: dense batch has %u rows per round, table has %u groups", in->count, t->G);
@@ -517,7 +518,7 @@ static rg::StepParams step_params(rg_table *t, const rg_batch_t *in)
 {
     rg::StepParams p{};
     p.t = t->dt;
-    p.rounds = in->rounds; p.count = in->count;
+    p.rounds = in->rounds; p.count = in->count; p.stride = in->count;
     p.entry_count = in->entry_count;
     p.counters = t->counters;
     p.wide_bodies = t->wide_bodies;
@@ -865,8 +866,10 @@ static int device_visible(rg_table *t, const void *p, const char *what, void **o
 }
 
 // rows == nullptr: the dense tick (rg_tick2_create: every group has a row); else the sparse one (rg_tick2_create_sparse: row i belongs to group rows->gid[i], the
-// rows of a run are counted by *rows->count, the per-row columns are sized for rows->capacity)
-static int tick2_create(rg_table_t *t, const rg_tick2_io_t *io, const rg_tick2_rows_t *rows, rg_tick2_t **tick, const char *who)
+// rows of a run are counted by *rows->count, the per-row columns are sized for rows->capacity). deep: the sparse tick of rg_tick2_create_sparse_rounds — io->rounds is
+// the greatest depth, every [round][row] column is laid out [io->rounds][capacity], and the depth of a run is read from *depth_now (nullptr: always io->rounds)
+static int tick2_create(rg_table_t *t, const rg_tick2_io_t *io, const rg_tick2_rows_t *rows, rg_tick2_t **tick, const char *who, bool deep = false,
+                        const uint32_t *depth_now = nullptr)
 {
     if (!t) return -1;
     if (int rc = compact_ok(t, who)) return rc;
@@ -879,7 +882,7 @@ static int tick2_create(rg_table_t *t, const rg_tick2_io_t *io, const rg_tick2_r
     if (io->expired_gid && (!io->expired_count || io->expired_capacity == 0)) return fail(t, -1, "%s: the expiry step needs expired_count and a capacity", who);
     if ((io->send_head == nullptr) != (io->send == nullptr)) return fail(t, -1, "%s: send_head and send come together", who);
     if (rows) {
-        if (io->rounds != 1) return fail(t, -1, "%s: %u rounds (a list of groups carries exactly one round)", who, io->rounds);
+        if (io->rounds != 1 && !deep) return fail(t, -1, "%s: %u rounds (a list of groups carries exactly one round)", who, io->rounds);
         if (!rows->gid || !rows->count) return fail(t, -1, "%s: gid and count are required", who);
         if (rows->capacity == 0 || rows->capacity > t->G) return fail(t, -1, "%s: a capacity of %u rows for %u groups (1 .. groups)", who, rows->capacity, t->G);
     }
@@ -890,10 +893,10 @@ static int tick2_create(rg_table_t *t, const rg_tick2_io_t *io, const rg_tick2_r
     wide.entry_terms = reinterpret_cast<const int64_t *>(io->entry_terms); wide.entry_count = io->entry_capacity;
     rg_reply_t dummy_r; rg_logfx_t dummy_l; rg_persist_t dummy_p;
     const rg_outcome_t shape{&dummy_r, &dummy_l, &dummy_p};
-    if (int rc = check_batch(t, &wide, &shape, false)) return rc;
+    if (int rc = check_batch(t, &wide, &shape, false, deep)) return rc;
     if (bind(t)) return -2;
-    void *d_head, *d_abcd, *d_terms, *d_now, *d_hb, *d_fl, *d_row, *d_per, *d_egid, *d_eep, *d_ecnt, *d_sh, *d_ss, *d_ready, *d_gid = nullptr, *d_cnt = nullptr;
-    if ((rows && (device_visible(t, rows->gid, "gid", &d_gid) || device_visible(t, rows->count, "count", &d_cnt))) ||
+    void *d_head, *d_abcd, *d_terms, *d_now, *d_hb, *d_fl, *d_row, *d_per, *d_egid, *d_eep, *d_ecnt, *d_sh, *d_ss, *d_ready, *d_gid = nullptr, *d_cnt = nullptr, *d_depth = nullptr;
+    if ((rows && (device_visible(t, rows->gid, "gid", &d_gid) || device_visible(t, rows->count, "count", &d_cnt) || device_visible(t, depth_now, "rounds", &d_depth))) ||
         device_visible(t, io->head, "head", &d_head) || device_visible(t, io->abcd, "abcd", &d_abcd) || device_visible(t, io->entry_terms, "entry_terms", &d_terms) ||
         device_visible(t, io->now, "now", &d_now) || device_visible(t, io->heartbeat, "heartbeat", &d_hb) || device_visible(t, io->in_flight, "in_flight", &d_fl) ||
         device_visible(t, io->row, "row", &d_row) || device_visible(t, io->persist32, "persist32", &d_per) || device_visible(t, io->expired_gid, "expired_gid", &d_egid) ||
@@ -930,6 +933,7 @@ static int tick2_create(rg_table_t *t, const rg_tick2_io_t *io, const rg_tick2_r
     fp.masks = (unsigned long long *)t->tick_masks; fp.ticket = t->tick_ticket;
     fp.out_gid = (uint32_t *)d_egid; fp.out_epoch = (uint32_t *)d_eep; fp.out_count = (uint32_t *)d_ecnt; fp.capacity = io->expired_capacity;
     fp.expire = io->expired_gid != nullptr;
+    fp.rounds_now = (const uint32_t *)d_depth;
     rg::TickTailParams tt{};
     tt.fp = fp; tt.qp = qp; tt.rp = rp; tt.critical_point = io->critical_point; tt.cool_down = io->cool_down_ms; tt.ready = (uint8_t *)d_ready;
     const char *nodes_env = getenv("RG_TICK_NODES");
@@ -975,6 +979,14 @@ int rg_tick2_create_sparse(rg_table_t *t, const rg_tick2_io_t *io, const rg_tick
 {
     if (t && !rows) return fail(t, -1, "rg_tick2_create_sparse: rows is NULL");
     return tick2_create(t, io, rows, tick, "rg_tick2_create_sparse");
+}
+
+int rg_tick2_create_sparse_rounds(rg_table_t *t, const rg_tick2_io_t *io, const rg_tick2_rounds_t *rows, rg_tick2_t **tick)
+{
+    if (t && !rows) return fail(t, -1, "rg_tick2_create_sparse_rounds: rows is NULL");
+    if (!t) return -1;
+    const rg_tick2_rows_t list{rows->gid, rows->count, rows->capacity};
+    return tick2_create(t, io, &list, tick, "rg_tick2_create_sparse_rounds", true, rows->rounds);
 }
 
 int rg_tick2_launch(rg_tick2_t *k)
@@ -1163,7 +1175,7 @@ int advance_bases(uint32_t rounds, uint32_t count, const uint32_t *gid, const rg
                          Flush flush)
 {
     if (!head || !index_base || window < 1 || window >= (1 << 30)) return -1;
-    if (gid ? (rounds != 1 || count > groups) : count != groups) return -2;
+    if (gid ? count > groups : count != groups) return -2;
     if (gid)
         for (uint32_t i = 0; i < count; i++)
             if (gid[i] >= groups) return -2;
@@ -1211,14 +1223,14 @@ static uint32_t host_index_fields(uint32_t kind)
 }
 
 /* compact rows in, compact outcome rows out (ABI 4), dense (rg_submit32c) or for a list of groups (rg_submit32c_sparse): see include/raftgpu.h */
-static int submit32c(rg_table_t *t, const rg_batch32_t *in, const rg_outcome32_t *out, int memspace, bool sparse, const char *who)
+static int submit32c(rg_table_t *t, const rg_batch32_t *in, const rg_outcome32_t *out, int memspace, bool sparse, const char *who, bool list_rounds = false)
 {
     if (!t) return -1;
     if (int rc = compact_ok(t, who)) return rc;
     if (!in || !out) return fail(t, -1, "%s: NULL batch or outcome", who);
     if (!in->head || !in->abcd || !out->row || !out->persist) return fail(t, -1, "%s: head, abcd, row and persist are required", who);
     if (!sparse && in->gid) return fail(t, -1, "rg_submit32c: dense batches only (gid must be NULL); a list of groups goes through rg_submit32c_sparse");
-    if (sparse && !in->gid) return fail(t, -1, "rg_submit32c_sparse: gid is required (dense batches go through rg_submit32c)");
+    if (sparse && !in->gid) return fail(t, -1, "%s: gid is required (dense batches go through rg_submit32c)", who);
     const int wides = (out->wide.reply != nullptr) + (out->wide.logfx != nullptr) + (out->wide.persist != nullptr);
     if (wides != 0 && wides != 3) return fail(t, -1, "%s: the overflow columns come as all three or none", who);
     rg_batch_t wide{};                              // the same shape rules as every other submission (rounds, count, gid list, entry bound)
@@ -1227,7 +1239,7 @@ static int submit32c(rg_table_t *t, const rg_batch32_t *in, const rg_outcome32_t
     wide.entry_terms = reinterpret_cast<const int64_t *>(in->entry_terms); wide.entry_count = in->entry_count;
     rg_reply_t dummy_r; rg_logfx_t dummy_l; rg_persist_t dummy_p;
     const rg_outcome_t shape{&dummy_r, &dummy_l, &dummy_p};
-    if (int rc = check_batch(t, &wide, &shape, memspace == RG_MEM_HOST)) return rc;
+    if (int rc = check_batch(t, &wide, &shape, memspace == RG_MEM_HOST, list_rounds)) return rc;
     if (in->count == 0) return 0;
     if (bind(t)) return -2;
     const size_t rows = (size_t)in->rounds * in->count;
@@ -1288,6 +1300,11 @@ int rg_submit32c(rg_table_t *t, const rg_batch32_t *in, const rg_outcome32_t *ou
 int rg_submit32c_sparse(rg_table_t *t, const rg_batch32_t *in, const rg_outcome32_t *out, int memspace)
 {
     return submit32c(t, in, out, memspace, true, "rg_submit32c_sparse");
+}
+
+int rg_submit32c_sparse_rounds(rg_table_t *t, const rg_batch32_t *in, const rg_outcome32_t *out, int memspace)
+{
+    return submit32c(t, in, out, memspace, true, "rg_submit32c_sparse_rounds", true);
 }
 
 /* host-side: rg_out32_t / rg_persist32_t rows -> the wide columns (no device involved) */

@@ -96,6 +96,8 @@ struct StepParams {
     int32_t require_fence;          // RG_OPT_REQUIRE_FENCED_TIMEOUTS: a TIMEOUT row with aux == 0 is RG_BAD_EVENT
     int32_t has_bases;              // the host has set a non-zero index base at some time (rg_index_base_set): 0 = the ibase column is all zero and is not read
     int32_t auto_window;            // RG_OPT_AUTO_INDEX_BASE: W > 0 raises a group's base to max(base, a - W) for every LOG_FLUSH row (absolute a), from the next launch on
+    uint32_t stride;                // list-of-groups launches: the rows between round r and r + 1 of every [round][row] column. It is `count` for a stand-alone
+                                    // submit; the sparse tick decides n <= capacity rows of columns laid out for the capacity. Dense launches address rounds with `count`
 };
 
 struct ReplicateParams {             // N1: Leader.replicateLog for many groups (rg_kernels.hip: replicate_kernel)
@@ -145,6 +147,8 @@ struct TickFoldParams {              // the device-resident tick's second kernel
     uint32_t *out_gid, *out_epoch, *out_count;
     uint32_t capacity;
     int expire;                      // 0: no expiry step
+    const uint32_t *rounds_now;      // the sparse tick with a depth of its own per run (rg_tick2_create_sparse_rounds): [1], device-visible, read when the graph runs;
+                                     // the depth is clamp(*rounds_now, 1, tp.rounds). nullptr: always tp.rounds (tick_depth in rg_kernels.hip)
 };
 struct TickTailParams {              // everything a recorded tick does after the decisions, one launch (rg_kernels.hip: tick_tail_kernel)
     TickFoldParams fp;

@@ -324,14 +324,15 @@ __global__ __launch_bounds__(256) void timers_emit_kernel(int64_t *deadline, con
 #endif
 // what the batch did to the timer and the follower statistics of group g (timers_update32_kernel + health_update_kernel); returns the deadline it leaves.
 // The group's row of round r is row r * p.tp.count + i of the batch's columns: i = g for a dense batch, the row that names g in a list of groups.
-__device__ __forceinline__ int64_t fold_rows_of(const TickFoldParams &p, const uint32_t g, const uint32_t i)
+// rounds = the rounds to fold: p.tp.rounds, or the depth of this run of a sparse tick that reads its depth when it runs (tick_depth).
+__device__ __forceinline__ int64_t fold_rows_of(const TickFoldParams &p, const uint32_t g, const uint32_t i, const uint32_t rounds)
 {
     const uint32_t G = p.tp.count;
     // RaftRoutine.resetTimer for the rows of this group (timers_update32_kernel)
     int64_t d = p.tp.deadline[g];
     uint32_t e = p.tp.epoch[g];
     const size_t GG = p.hp.t.groups;
-    for (uint32_t r = 0; r < p.tp.rounds; r++) {
+    for (uint32_t r = 0; r < rounds; r++) {
         const size_t row = (size_t)r * G + i;
         const uint32_t flags = (uint32_t)p.tp.out32[row].y;
         const int64_t now = p.tp.now_mem[r];
@@ -355,16 +356,24 @@ __device__ __forceinline__ int64_t fold_rows_of(const TickFoldParams &p, const u
     p.tp.epoch[g] = e;
     return d;
 }
-__device__ __forceinline__ int64_t fold_group(const TickFoldParams &p, const uint32_t g) { return fold_rows_of(p, g, g); }
+__device__ __forceinline__ int64_t fold_group(const TickFoldParams &p, const uint32_t g) { return fold_rows_of(p, g, g, p.tp.rounds); }
+// the depth of THIS run of a sparse tick: clamp(*rounds_now, 1, the depth it was recorded for), read when the graph runs like the row count; uniform
+__device__ __forceinline__ uint32_t tick_depth(const TickFoldParams &p)
+{
+    const uint32_t most = p.tp.rounds;
+    if (p.rounds_now == nullptr) return most;
+    const uint32_t given = *p.rounds_now;
+    return given < 1u ? 1u : (given > most ? most : given);
+}
 
 // The fired tickets of the whole table, in ascending gid order (see above). EVERY thread of the grid calls it (the barriers); d = the deadline of the lane's
 // group g, `holds` (wave-uniform) = this wavefront has groups at all (lane = group); `part` = at least 136 words of the workgroup's LDS.
-__device__ __forceinline__ void expire_tail(const TickFoldParams &p, const int64_t d, const uint32_t g, const bool holds, const bool active, uint32_t *part)
+// now = the clock of the expiry.
+__device__ __forceinline__ void expire_tail(const TickFoldParams &p, const int64_t now, const int64_t d, const uint32_t g, const bool holds, const bool active, uint32_t *part)
 {
     constexpr unsigned long long ST_COUNT = 1ull << 62, ST_PREFIX = 2ull << 62;
     constexpr uint32_t GEN_MASK = 0x3FFFFFFFu;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, nwaves = blockDim.x >> 6;
-    const int64_t now = *p.now_last;
     const bool fired = holds && active && d > 0 && d <= now;
     const unsigned long long m = __ballot(fired);
     const uint32_t rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
@@ -427,6 +436,11 @@ __device__ __forceinline__ void expire_tail(const TickFoldParams &p, const int64
             p.tp.deadline[g] = -1;                                    // electionTimeout's CAS: deadline -> TimerTicket.TIMEOUT
         }
     }
+}
+// (the recordings whose depth is fixed: the clock of the last round, at the address worked out when the tick was recorded)
+__device__ __forceinline__ void expire_tail(const TickFoldParams &p, const int64_t d, const uint32_t g, const bool holds, const bool active, uint32_t *part)
+{
+    expire_tail(p, *p.now_last, d, g, holds, active, part);
 }
 
 __global__ __launch_bounds__(256) void tick_fold_kernel(const TickFoldParams p)
@@ -610,7 +624,9 @@ hipError_t launch_tick(const StepParams &p, const TickTailParams &tp, int follow
 // ---- the SPARSE recorded tick (rg_tick2_create_sparse): the same for a LIST of groups whose length changes from run to run --------------------------------
 // Most groups of a 100-us tick have no event, and tick_kernel reads and writes all of them all the same. Here a workgroup is 64 ROWS: row i of every per-row
 // column belongs to group gid[i], the columns are sized for p0.count = the tick's capacity, and the rows of THIS run — n = min(*rows_now, capacity) — are read
-// from device-visible memory when the graph runs, like the clocks. Workgroups past the last row leave at once; the others decide their rows with the
+// from device-visible memory when the graph runs, like the clocks. So is its DEPTH (rg_tick2_create_sparse_rounds): R = tick_depth(tp.fp) of the p0.rounds rounds the
+// columns hold, round r of every [round][row] column at r * capacity (p0.stride), whatever n and R are; the tail folds R rounds and takes the send rows and the
+// readiness at now[R - 1]. Rows >= n and rounds >= R are neither read nor written. Workgroups past the last row leave at once; the others decide their rows with the
 // list-of-groups instantiations of the step bodies on a LOCAL copy of the parameters whose count is n (so the lanes past n shadow row n - 1 and store nothing
 // beyond it) and then do tick_kernel's tail for them: fold, send rows, readiness — through gid. A table built with RG_FORCE_WIDE=1 leaves the 32-bit body at its
 // state load, as every compact launch of such a table does. The expiry is not here: it covers the whole table, whatever the list — tick_expire_kernel, next node.
@@ -619,10 +635,14 @@ __global__ __launch_bounds__(2 * BLOCK) __attribute__((amdgpu_waves_per_eu(WAVES
 {
     __shared__ alignas(16) unsigned char smem[SplitLds<F, true, 2>::BYTES];
     static_assert(SplitLds<F, true, 2>::BYTES >= 3 * 64 * 16, "the tail's staging rows reuse the step's LDS");
-    const uint32_t given = *rows_now, n = given < p0.count ? given : p0.count;
+    // (n and the depth are loaded through pointers held in by-value structs: readfirstlane states what they are — the same for every lane — so the round
+    //  loops of the bodies count in a scalar register whatever the compiler can prove about the loads)
+    const uint32_t given = __builtin_amdgcn_readfirstlane(*rows_now), n = given < p0.count ? given : p0.count;
     if (blockIdx.x * (uint32_t)BLOCK >= n) return;           // (workgroup-uniform: nobody is left waiting at a barrier; n = 0 is a tick without rows)
+    const uint32_t depth = __builtin_amdgcn_readfirstlane(tick_depth(tp.fp));
     StepParams p = p0;
     p.count = n;
+    p.rounds = depth;
     if (!narrow_body<F, true, true, 1, 1>(p, smem)) {
         if (threadIdx.x == 0) { RG_NOTE_FALLBACK(); atomicAdd(p.wide_bodies, 1ull); }
         lds_barrier();
@@ -638,29 +658,29 @@ __global__ __launch_bounds__(2 * BLOCK) __attribute__((amdgpu_waves_per_eu(WAVES
     const bool in_list = row < n;
     const uint32_t g = p.gid[in_list ? row : n - 1u];
     if (holds) {
-        if (in_list) fold_rows_of(tp.fp, g, row);
+        if (in_list) fold_rows_of(tp.fp, g, row, depth);
     } else if (tp.qp.head != nullptr) {
         ReplicateParams qp = tp.qp;
         qp.count = n;                                        // (the rows of this run; in_flight / send keep the capacity's layout: the stride)
         replicate_wave<F>(qp, stage, blockIdx.x * BLOCK, lane, p0.count);
     }
     __syncthreads();
-    if (!holds && tp.ready != nullptr && in_list) tp.ready[row] = ready_of(tp.rp, *tp.rp.now_mem, tp.critical_point, tp.cool_down, g);
+    if (!holds && tp.ready != nullptr && in_list) tp.ready[row] = ready_of(tp.rp, tp.fp.tp.now_mem[depth - 1u], tp.critical_point, tp.cool_down, g);
 }
-// the fired tickets of the whole table at now[0], one lane per group: the sparse tick's second node (expire_tail as the dense kernels call it)
+// the fired tickets of the whole table at the clock of the run's last round, now[R - 1], one lane per group: the sparse tick's second node (expire_tail as the dense kernels call it)
 __global__ __launch_bounds__(256) void tick_expire_kernel(const TickFoldParams p)
 {
     __shared__ uint32_t part[136];
     const uint32_t g = blockIdx.x * 256u + threadIdx.x;
     const bool active = g < p.tp.groups;
     const int64_t d = active ? p.tp.deadline[g] : 0;
-    expire_tail(p, d, g, true, active, part);
+    expire_tail(p, p.tp.now_mem[tick_depth(p) - 1u], d, g, true, active, part);
 }
 // p.count = the capacity (1 .. groups): what the per-row columns are sized for, and the grid
 hipError_t launch_tick_sparse(const StepParams &p, const TickTailParams &tp, const uint32_t *rows_now, int followers, hipStream_t s)
 {
     const uint32_t blocks = (p.count + BLOCK - 1) / BLOCK;
-    if (blocks == 0 || p.count >= (1u << 28) || p.out32 == nullptr || p.gid == nullptr || rows_now == nullptr || p.rounds != 1u) return hipErrorInvalidValue;
+    if (blocks == 0 || p.count >= (1u << 28) || p.out32 == nullptr || p.gid == nullptr || rows_now == nullptr || p.rounds == 0u || p.rounds > 64u || p.stride != p.count || tp.fp.tp.rounds != p.rounds) return hipErrorInvalidValue;
     const bool many = blocks > 1024u;
     const dim3 grid(blocks), wg(2 * BLOCK);
     switch (followers) {

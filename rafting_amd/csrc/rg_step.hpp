@@ -383,6 +383,7 @@ __global__ __launch_bounds__(BLOCK, 1) void step_kernel(const StepParams p)
     // loop has no divergent control flow around it — and only their stores are switched off.
     const uint32_t ir = active ? i : p.count - 1u;
     const uint32_t gi = SPARSE ? p.gid[ir] : ir;
+    const uint32_t round_rows = SPARSE ? p.stride : p.count;      // rows between two rounds of a [round][row] column (StepParams.stride)
 
     Group g;
     load_group(p.t, gi, g);
@@ -391,7 +392,7 @@ __global__ __launch_bounds__(BLOCK, 1) void step_kernel(const StepParams p)
     EventTail cur_t{}, near_t{};
     const uint32_t last_round = p.rounds - 1u;            // the host never launches with rounds == 0
     load_event<false>(p, ir, cur);
-    load_event<false>(p, (size_t)(last_round < 1u ? last_round : 1u) * p.count + ir, near);
+    load_event<false>(p, (size_t)(last_round < 1u ? last_round : 1u) * round_rows + ir, near);
     PeersWide<F> pe;
     pe.e = sh_epoch + lane; pe.n = sh_next + lane; pe.m = sh_match + lane; pe.r = sh_rej + lane; pe.overflow = false;
     stage_peers<F>(p.t, gi, g, pe);
@@ -413,7 +414,7 @@ __global__ __launch_bounds__(BLOCK, 1) void step_kernel(const StepParams p)
     // round, for memory operations issued a full round earlier, so their latency overlaps decision work.
     load_event_tail<false>(p, ir, cur, cur_t);
     for (uint32_t r = 0; r < p.rounds; r++) {
-        const size_t row = (size_t)r * p.count + ir;
+        const size_t row = (size_t)r * round_rows + ir;
         // Drain HERE, before issuing anything new: the vm counter retires in order and (on gfx9-class ISAs)
         // counts stores too, so (a) a wait placed lazily inside the divergent decision code would degrade to
         // vmcnt(0) and also wait for the loads issued below, and (b) draining right after the outcome stores
@@ -421,14 +422,14 @@ __global__ __launch_bounds__(BLOCK, 1) void step_kernel(const StepParams p)
         // issued right after this point and get a whole round of decision work to complete.
         __builtin_amdgcn_s_waitcnt(0x0F70);         // vmcnt(0) expcnt(7) lgkmcnt(15)
         if (r > 0) {
-            if (active) nt_store16(p.reply + (row - p.count), pend_rep);
-            if (pend_w_lfx) nt_store16(p.logfx + (row - p.count), pend_lfx);
-            if (pend_w_per) nt_store16(p.persist + (row - p.count), pend_per);
+            if (active) nt_store16(p.reply + (row - round_rows), pend_rep);
+            if (pend_w_lfx) nt_store16(p.logfx + (row - round_rows), pend_lfx);
+            if (pend_w_per) nt_store16(p.persist + (row - round_rows), pend_per);
         }
         // prefetch without conditions: past the last round the pipeline simply re-reads the last round's rows
         const uint32_t r1 = r + 1u < p.rounds ? r + 1u : last_round, r2 = r + 2u < p.rounds ? r + 2u : last_round;
-        load_event<false>(p, (size_t)r2 * p.count + ir, far);
-        load_event_tail<false>(p, (size_t)r1 * p.count + ir, near, near_t);
+        load_event<false>(p, (size_t)r2 * round_rows + ir, far);
+        load_event_tail<false>(p, (size_t)r1 * round_rows + ir, near, near_t);
 
         {
             const uint32_t kind = RG_HDR_KIND(cur.hdr);
@@ -463,7 +464,7 @@ __global__ __launch_bounds__(BLOCK, 1) void step_kernel(const StepParams p)
         near = far;
     }
     if (active) {
-        const size_t row = (size_t)(p.rounds - 1) * p.count + ir;
+        const size_t row = (size_t)(p.rounds - 1) * round_rows + ir;
         nt_store16(p.reply + row, pend_rep);
         if (pend_w_lfx) nt_store16(p.logfx + row, pend_lfx);
         if (pend_w_per) nt_store16(p.persist + row, pend_per);
@@ -542,9 +543,10 @@ __device__ __forceinline__ void split_body(const StepParams &p, unsigned char *s
     const bool active = i < p.count;
     const uint32_t ir = active ? i : p.count - 1u;       // lanes past the end shadow the last row; only their stores are off
     const uint32_t last_round = p.rounds - 1u;
+    const uint32_t round_rows = SPARSE ? p.stride : p.count;      // rows between two rounds of a [round][row] column (StepParams.stride)
 
     if (io_wave) {
-        auto row_of = [&](uint32_t r) { return (size_t)(r < p.rounds ? r : last_round) * p.count + ir; };
+        auto row_of = [&](uint32_t r) { return (size_t)(r < p.rounds ? r : last_round) * round_rows + ir; };
         // compact rows (and compact outcome rows) carry log indices relative to the group's index base (rg_device.hpp: to_rel): this body decides on
         // absolute values, so the row's index fields are taken off the base as they are handed over, and put back on it in the rows of OUT32
         int64_t io_base = 0;
@@ -571,7 +573,7 @@ __device__ __forceinline__ void split_body(const StepParams &p, unsigned char *s
         Tally tally;
         auto retire = [&](uint32_t r, uint32_t hdr) {      // outcome of round r: LDS -> global, plus the tallies
             const uint32_t slot = r & 1u;
-            const size_t row = (size_t)r * p.count + ir;
+            const size_t row = (size_t)r * round_rows + ir;
             const uint64_t fe = sh_out[slot][OUT_FLAGS][lane];
             const uint32_t flags_all = (uint32_t)fe, flags = flags_all & 0xFFFFu, status = RG_F_STATUS(flags_all);
             rg_reply_t rep;
@@ -838,7 +840,7 @@ __device__ __forceinline__ bool narrow_body(const StepParams &p, unsigned char *
                  b_logfx = reinterpret_cast<uint64_t>(p.logfx),
                  b_persist = OUT32 ? reinterpret_cast<uint64_t>(p.persist32) : reinterpret_cast<uint64_t>(p.persist);
         RG_OWN_SGPRS(b_head); RG_OWN_SGPRS(b_q); RG_OWN_SGPRS(b_reply); RG_OWN_SGPRS(b_logfx); RG_OWN_SGPRS(b_persist);
-        const uint64_t round_rows = p.count;
+        const uint64_t round_rows = SPARSE ? p.stride : p.count;      // (a scalar either way: StepParams.stride)
         const uint32_t irm = ir & 0x0FFFFFFFu;           // (spelled out for the instruction selector: ir < count < 2^28)
         // the group's index base: only the wide effect rows need it (compact outcome rows carry indices relative to it, like the event rows)
         int64_t io_base = 0;

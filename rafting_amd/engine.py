@@ -31,7 +31,7 @@ def exported_symbols():
     """Every entry point include/raftgpu.h declares."""
     return [
         "rg_abi_version", "rg_table_create", "rg_table_destroy", "rg_last_error", "rg_table_groups",
-        "rg_table_cluster", "rg_table_option", "rg_load_state", "rg_read_state", "rg_submit", "rg_submit32", "rg_submit32c", "rg_submit32c_sparse", "rg_outcome32_unpack", "rg_outcome32_unpack_rel", "rg_index_base_set", "rg_index_base_get", "rg_index_base_advance", "rg_index_base_advance32", "rg_batch32_pack_rel", "rg_batch32_pack", "rg_submit_async", "rg_submit_async_packed", "rg_submit_wait", "rg_tick_create", "rg_tick_launch", "rg_tick_wait", "rg_tick_destroy", "rg_tick2_create", "rg_tick2_create_sparse", "rg_tick2_launch", "rg_tick2_wait", "rg_tick2_destroy", "rg_timers_update32", "rg_health_update32", "rg_sync", "rg_step_kernel", "rg_host_alloc", "rg_host_free", "rg_dev_alloc",
+        "rg_table_cluster", "rg_table_option", "rg_load_state", "rg_read_state", "rg_submit", "rg_submit32", "rg_submit32c", "rg_submit32c_sparse", "rg_submit32c_sparse_rounds", "rg_outcome32_unpack", "rg_outcome32_unpack_rel", "rg_index_base_set", "rg_index_base_get", "rg_index_base_advance", "rg_index_base_advance32", "rg_batch32_pack_rel", "rg_batch32_pack", "rg_submit_async", "rg_submit_async_packed", "rg_submit_wait", "rg_tick_create", "rg_tick_launch", "rg_tick_wait", "rg_tick_destroy", "rg_tick2_create", "rg_tick2_create_sparse", "rg_tick2_create_sparse_rounds", "rg_tick2_launch", "rg_tick2_wait", "rg_tick2_destroy", "rg_timers_update32", "rg_health_update32", "rg_sync", "rg_step_kernel", "rg_host_alloc", "rg_host_free", "rg_dev_alloc",
         "rg_dev_free", "rg_copy_to_device", "rg_copy_to_host", "rg_stream", "rg_replicate", "rg_timers_configure", "rg_timers_update",
         "rg_timers_expired", "rg_timers_expired_epochs", "rg_timers_arm", "rg_timers_read", "rg_health_update", "rg_health_failure", "rg_ready", "rg_health_read",
         "rg_timing_enable",
@@ -106,6 +106,7 @@ def lib():
             real, L = L, _Tolerant(L)
         L.rg_submit32c.argtypes = [vp, C.POINTER(abi.CBatch32), C.POINTER(abi.COutcome32), i32]
         L.rg_submit32c_sparse.argtypes = [vp, C.POINTER(abi.CBatch32), C.POINTER(abi.COutcome32), i32]
+        L.rg_submit32c_sparse_rounds.argtypes = [vp, C.POINTER(abi.CBatch32), C.POINTER(abi.COutcome32), i32]
         L.rg_outcome32_unpack.argtypes = [C.POINTER(abi.COutcome32), u32, u32, vp, C.POINTER(abi.COutcome)]
         L.rg_outcome32_unpack_rel.argtypes = [C.POINTER(abi.COutcome32), u32, u32, vp, vp, C.POINTER(abi.COutcome)]
         L.rg_index_base_set.argtypes = [vp, u32, u32, vp]
@@ -126,6 +127,7 @@ def lib():
         L.rg_tick_destroy.argtypes = [vp]
         L.rg_tick2_create.argtypes = [vp, C.POINTER(abi.CTick2Io), C.POINTER(vp)]
         L.rg_tick2_create_sparse.argtypes = [vp, C.POINTER(abi.CTick2Io), C.POINTER(abi.CTick2Rows), C.POINTER(vp)]
+        L.rg_tick2_create_sparse_rounds.argtypes = [vp, C.POINTER(abi.CTick2Io), C.POINTER(abi.CTick2Rounds), C.POINTER(vp)]
         L.rg_tick2_launch.argtypes = [vp]
         L.rg_tick2_wait.argtypes = [vp]
         L.rg_tick2_destroy.argtypes = [vp]
@@ -296,7 +298,9 @@ class PackedBatch:
 
 def unpack32(out32, rounds, count, role_epoch_before, index_base=None):
     """abi.Outcome32 -> abi.Outcome through the library's host-side rg_outcome32_unpack(_rel). `role_epoch_before`: the groups' role epochs before the
-    batch (GroupState.role_epoch); index_base: the groups' index bases (None: all 0); returns (outcome, role epochs after the batch)."""
+    batch (GroupState.role_epoch); index_base: the groups' index bases (None: all 0); returns (outcome, role epochs after the batch).
+    A list of groups, with any number of rounds: both arrays gathered per listed group ([count], e.g. state.role_epoch[gid]); the role epochs are
+    chained per row across the rounds."""
     out = abi.Outcome(rounds * count)
     ep = np.ascontiguousarray(role_epoch_before, dtype=np.uint32).copy()
     assert len(ep) == count and out32.rows == rounds * count
@@ -348,10 +352,18 @@ class Tick2:
     only the device consumes into HBM (rg_dev_alloc).  refill(batch, now[, heartbeat, in_flight]) writes the next tick's rows and clocks.
     sparse_cap=N records the SPARSE tick (rg_tick2_create_sparse): refill takes a batch with a gid list of n <= N rows, every per-row column is indexed by
     row (heartbeat [n]; in_flight follower-major for those n rows), outcome32() / sends() / readiness() return the n rows of the last refill; the expired
-    list still describes the whole table. The row count always lives in page-locked host memory."""
+    list still describes the whole table. The row count always lives in page-locked host memory.
+    sparse_cap=N, sparse_rounds=True records the sparse tick WITH A DEPTH (rg_tick2_create_sparse_rounds): `rounds` is the greatest depth, refill takes a batch
+    with a gid list and b.rounds <= rounds, writes round r of every [round][row] column at r * N and sets the count and the depth (both in page-locked host
+    memory); `now` holds b.rounds clocks. outcome32() returns the b.rounds x n rows of the last refill as one contiguous [R][n] image.
+    depth_pointer=False records it without a `rounds` pointer: every refill then carries exactly `rounds` rounds."""
 
-    def __init__(self, table, rounds, entry_cap=0, expired_cap=None, send=True, ready=True, critical_point=0, cool_down_ms=0, device_resident=False, sparse_cap=None):
+    def __init__(self, table, rounds, entry_cap=0, expired_cap=None, send=True, ready=True, critical_point=0, cool_down_ms=0, device_resident=False, sparse_cap=None,
+                 sparse_rounds=False, depth_pointer=True):
         F = table.cluster - 1
+        if sparse_rounds and sparse_cap is None:
+            raise EngineError("Tick2: sparse_rounds belongs to the sparse tick (give sparse_cap)")
+        self.deep, self.depth, self.fixed_depth = bool(sparse_rounds), rounds, not depth_pointer      # (depth: the rounds of the last refill)
         G = table.groups if sparse_cap is None else int(sparse_cap)      # (G: the rows every per-row column is sized for)
         self.table, self.rounds, self.G, self.F, self.sparse = table, rounds, G, F, sparse_cap is not None
         self.n = G                                                        # rows of the last refill
@@ -393,10 +405,18 @@ class Tick2:
         h = C.c_void_p()
         if self.sparse:
             self.gid, self.count = big(np.uint32, G), col(np.uint32, 1)
-            rw = abi.CTick2Rows()
-            rw.gid, rw.count, rw.capacity = addr(self.gid), addr(self.count), G
-            self.rows = rw
-            table._check(lib().rg_tick2_create_sparse(table._h, C.byref(io), C.byref(rw), C.byref(h)))
+            if self.deep:
+                self.depth_now = col(np.uint32, 1)
+                self.depth_now[0] = rounds
+                rw = abi.CTick2Rounds()
+                rw.gid, rw.count, rw.rounds, rw.capacity = addr(self.gid), addr(self.count), (None if self.fixed_depth else addr(self.depth_now)), G
+                self.rows = rw
+                table._check(lib().rg_tick2_create_sparse_rounds(table._h, C.byref(io), C.byref(rw), C.byref(h)))
+            else:
+                rw = abi.CTick2Rows()
+                rw.gid, rw.count, rw.capacity = addr(self.gid), addr(self.count), G
+                self.rows = rw
+                table._check(lib().rg_tick2_create_sparse(table._h, C.byref(io), C.byref(rw), C.byref(h)))
         else:
             table._check(lib().rg_tick2_create(table._h, C.byref(io), C.byref(h)))
         self._h = h
@@ -414,8 +434,8 @@ class Tick2:
         return src.to_host(dtype, n) if isinstance(src, DeviceBuffer) else np.array(src[:n], copy=True)
 
     def refill(self, batch, now, heartbeat=None, in_flight=None, index_base=None):
-        if self.sparse and batch.count == 0:               # a tick without rows: only the clock and the count travel
-            self.now[:] = np.asarray(now, dtype=np.int64)
+        if self.sparse and batch.count == 0:               # a tick without rows: only the clock(s) and the count (and the depth) travel
+            self._clocks(now)
             self.count[0] = self.n = 0
             return
         b32 = batch if isinstance(batch, abi.Batch32) else pack32(batch, index_base)
@@ -432,16 +452,29 @@ class Tick2:
         if in_flight is not None or not isinstance(self.in_flight, DeviceBuffer):
             self._put(self.in_flight, np.zeros(self.F * self.G, np.uint16) if in_flight is None else np.ascontiguousarray(np.asarray(in_flight, dtype=np.uint16).reshape(-1)))
 
+    def _clocks(self, now):
+        """the clocks of a refill; the sparse tick with a depth: one per round of THIS tick, which also sets the depth"""
+        now = np.asarray(now, dtype=np.int64).reshape(-1)
+        if not self.deep:
+            self.now[:] = now
+            return
+        assert (len(now) == self.rounds) if self.fixed_depth else (1 <= len(now) <= self.rounds)
+        self.now[: len(now)] = now
+        self.depth_now[0] = self.depth = len(now)
+
     def _refill_rows(self, b32, now, heartbeat, in_flight):
-        """the sparse tick: n = b32.count rows for the groups b32.gid names; rows n .. capacity - 1 of every column keep what they held"""
+        """the sparse tick: n = b32.count rows for the groups b32.gid names; rows n .. capacity - 1 of every column keep what they held
+        (with a depth: round r of the batch goes to r * capacity, rounds b32.rounds .. keep what they held)"""
         n = b32.count
-        assert b32.rounds == 1 and b32.gid is not None and len(b32.gid) == n <= self.G and b32.entry_count <= self.io.entry_capacity
+        assert b32.gid is not None and len(b32.gid) == n <= self.G and b32.entry_count <= self.io.entry_capacity
+        assert (1 <= b32.rounds <= self.rounds and len(np.atleast_1d(now)) == b32.rounds) if self.deep else b32.rounds == 1
         self._put(self.gid, np.ascontiguousarray(b32.gid, dtype=np.uint32))
-        self._put(self.head, b32.head[:n])
-        self._put(self.abcd, b32.abcd[:n])
+        for r in range(b32.rounds):
+            self._put(self.head, b32.head[r * n: (r + 1) * n], at=r * self.G)
+            self._put(self.abcd, b32.abcd[r * n: (r + 1) * n], at=r * self.G)
         if b32.entry_count:
             self._put(self.entry_terms, b32.entry_terms[: b32.entry_count])
-        self.now[:] = np.asarray(now, dtype=np.int64)
+        self._clocks(now)
         self._put(self.heartbeat, np.zeros(n, np.uint8) if heartbeat is None else np.ascontiguousarray(heartbeat, dtype=np.uint8).reshape(n))
         fl = np.zeros((self.F, n), np.uint16) if in_flight is None else np.ascontiguousarray(np.asarray(in_flight, dtype=np.uint16).reshape(self.F, n))
         for j in range(self.F):                            # element (j, row) at j * capacity + row
@@ -456,6 +489,13 @@ class Tick2:
         self.table._check(lib().rg_tick2_wait(self._h))
 
     def outcome32(self):
+        if self.deep:                                      # [R][n] of the [rounds][capacity] columns, contiguous
+            R, n = self.depth, self.n
+            out = abi.Outcome32(R * n, wide=False)
+            row = self._get(self.row, abi.OUT32_DT, self.rounds * self.G).reshape(self.rounds, self.G)
+            per = self._get(self.persist32, abi.PERSIST32_DT, self.rounds * self.G).reshape(self.rounds, self.G)
+            out.row, out.persist = np.ascontiguousarray(row[:R, :n]).reshape(-1), np.ascontiguousarray(per[:R, :n]).reshape(-1)
+            return out
         rows = self.rounds * self.n
         out = abi.Outcome32(rows, wide=False)
         out.row, out.persist = self._get(self.row, abi.OUT32_DT, rows), self._get(self.persist32, abi.PERSIST32_DT, rows)
@@ -710,6 +750,15 @@ class Table:
         out32 = abi.Outcome32(b32.rounds * b32.count, fill, wide=wide) if out32 is None else out32
         b, o = b32.as_struct(), out32.as_struct()
         self._check(lib().rg_submit32c_sparse(self._h, C.byref(b), C.byref(o), abi.MEM_HOST))
+        return out32
+
+    def submit32c_sparse_rounds(self, batch, out32=None, fill=0, wide=True, index_base=None):
+        """rg_submit32c_sparse for R >= 1 rounds in one launch (rg_submit32c_sparse_rounds, RG_MEM_HOST): `batch` carries a gid list and batch.rounds rounds,
+        row (r, i) at r * count + i for group gid[i]; the abi.Outcome32 is laid out the same way"""
+        b32 = batch if isinstance(batch, abi.Batch32) else pack32(batch, index_base)
+        out32 = abi.Outcome32(b32.rounds * b32.count, fill, wide=wide) if out32 is None else out32
+        b, o = b32.as_struct(), out32.as_struct()
+        self._check(lib().rg_submit32c_sparse_rounds(self._h, C.byref(b), C.byref(o), abi.MEM_HOST))
         return out32
 
     def submit32c_unpacked(self, batch, role_epoch_before, fill=0):
