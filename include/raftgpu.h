@@ -63,12 +63,14 @@ extern "C" {
                                      5: the device-resident tick on compact outcome rows: rg_timers_update32, rg_health_update32, rg_tick2_*; clusters of up to 15 nodes
                                      6: automatic index bases: RG_OPT_AUTO_INDEX_BASE, rg_index_base_advance / rg_index_base_advance32
                                         (still 6, new symbols only — nothing that existed changed: rg_submit32c_sparse, rg_tick2_rows_t, rg_tick2_create_sparse;
-                                         then rg_submit32c_sparse_rounds, rg_tick2_rounds_t, rg_tick2_create_sparse_rounds: a list of groups with R rounds) */
+                                         then rg_submit32c_sparse_rounds, rg_tick2_rounds_t, rg_tick2_create_sparse_rounds: a list of groups with R rounds;
+                                         then RG_OPT_COMPACT_ANY_CLUSTER: a new value of the option enum, no new symbol, no struct change) */
 #define RG_MIN_CLUSTER      2     /* P: cluster size incl. self (RaftCluster.size()) */
 #define RG_MAX_CLUSTER      15    /* (ABI 5; the slot field of a row header is 4 bits. Leadership.majorIndices sorts any number of followers, member/Leadership.java:116-130.)
-                                     Clusters of up to RG_MAX_COMPACT_CLUSTER nodes have every kernel; larger ones are decided by the wide-row kernels only:
-                                     rg_submit / rg_submit_async take them, the compact formats (rg_submit32*, rg_submit_async_packed, rg_tick*) answer -1 */
-#define RG_MAX_COMPACT_CLUSTER 7
+                                     Every cluster size has the wide-row entry points (rg_submit, rg_submit_async). The compact formats (rg_submit32*, rg_submit_async_packed)
+                                     and the ticks (rg_tick_*, rg_tick2_*) take clusters of up to RG_MAX_COMPACT_CLUSTER nodes as they are, and larger ones — up to
+                                     RG_MAX_CLUSTER — for a table that has RG_OPT_COMPACT_ANY_CLUSTER; without the option they answer -1 for such a table. */
+#define RG_MAX_COMPACT_CLUSTER 7  /* what the compact formats and the ticks take WITHOUT the option (unchanged by it) */
 #define RG_TERM_RUNS        4     /* K: cached term runs of the log tail per group */
 #define RG_NO_NODE          (-1)  /* Java null for a RaftCluster.ID */
 
@@ -278,9 +280,20 @@ const char *rg_last_error(const rg_table_t *t);      /* t may be NULL for create
  * row names the participant whose ticket fired (rg_timers_expired_epochs supplies it) — the ordering contract of INTEGRATION.md section 1,
  * enforced instead of merely stated. The C++ host's IngressFlusher turns it on. */
 enum { RG_OPT_REQUIRE_FENCED_TIMEOUTS = 1,
-       RG_OPT_AUTO_INDEX_BASE = 2 };        /* (ABI 6) value = the window W of the automatic index bases: 0 = off (default), 1 <= W < 2^30 = on, anything else -1.
+       RG_OPT_AUTO_INDEX_BASE = 2,          /* (ABI 6) value = the window W of the automatic index bases: 0 = off (default), 1 <= W < 2^30 = on, anything else -1.
                                                See "THE INDEX BASE OF THE COMPACT FORMATS" below. Switching it on or off bumps what a recorded tick has baked in:
                                                rg_tick_launch / rg_tick2_launch of an earlier recording then refuse (-1). Recommended window: 2^28. */
+       RG_OPT_COMPACT_ANY_CLUSTER = 3 };    /* value 0 (default): the compact formats and the ticks refuse a table of more than RG_MAX_COMPACT_CLUSTER nodes (-1, "wide rows").
+                                               value 1: they take the table's cluster size, whatever it is (2 .. RG_MAX_CLUSTER): rg_submit32, rg_submit32c, rg_submit32c_sparse,
+                                               rg_submit32c_sparse_rounds, rg_submit_async_packed, rg_tick_create, rg_tick2_create, rg_tick2_create_sparse,
+                                               rg_tick2_create_sparse_rounds — same rows, same outcomes, bit-identical to the wide-row entry points. Any other value: -1.
+                                               A table of up to RG_MAX_COMPACT_CLUSTER nodes is decided by the same kernels with the option on or off. Switching it bumps
+                                               what a recorded tick has baked in, like the other options: a recording made under one setting refuses to launch under the
+                                               other. COST at 8 .. 15 nodes: the compact-row kernels keep one matchIndex per follower in registers and one record per
+                                               follower in LDS (25 KB per workgroup at 7 followers, 38 KB at 14), so fewer workgroups share a CU than at 5 nodes: three
+                                               wavefronts per SIMD at 8 followers, two at 14. Its rate against the wide-row kernels has NOT been measured yet (DESIGN.md
+                                               section 6, "Compact rows above 7 nodes", names the measurement): until it is, the option buys the formats and the ticks,
+                                               not a known speed. The C++ ingress / flusher and the Java row packer do not set the option. */
 int         rg_table_option(rg_table_t *t, int option, int value);
 uint32_t    rg_table_groups(const rg_table_t *t);
 uint32_t    rg_table_cluster(const rg_table_t *t);
@@ -652,7 +665,8 @@ int rg_tick2_create_sparse(rg_table_t *t, const rg_tick2_io_t *io, const rg_tick
  * With rounds == NULL or *rounds == io->rounds, the list gid[i] = i and n = capacity = groups, every column equals the dense io->rounds-round tick's; with
  * io->rounds == 1 every column equals rg_tick2_create_sparse's. The handle is an ordinary rg_tick2_t: launch / wait / destroy, the refusal after a change of options or
  * index bases and a tick that outlives its table are all as above. Refused before anything is recorded, each with a message: a missing gid / count, a capacity of 0 or
- * above the group count, io->rounds outside 1 .. 64, a column or a `rounds` that is not device-visible, a cluster above RG_MAX_COMPACT_CLUSTER. */
+ * above the group count, io->rounds outside 1 .. 64, a column or a `rounds` that is not device-visible, a cluster above RG_MAX_COMPACT_CLUSTER unless the table has
+ * RG_OPT_COMPACT_ANY_CLUSTER. */
 typedef struct {
     const uint32_t *gid;       /* [capacity] as rg_tick2_rows_t */
     const uint32_t *count;     /* [1] rows of THIS tick, n = min(*count, capacity), read when the graph runs */

@@ -16,6 +16,7 @@ public final class GpuTable implements AutoCloseable {
 
     public static final int ABI = 5;
     public static final int OPT_REQUIRE_FENCED_TIMEOUTS = 1;
+    public static final int OPT_COMPACT_ANY_CLUSTER = 3;       // raftgpu.h: the compact formats and the ticks for clusters above 7 nodes (not set here: the row packer stays on wide rows for them)
 
     final long handle;
     public final int groups, cluster, selfSlot;

@@ -43,6 +43,7 @@ NEED_HOST, SKIPPED_AFTER_NEED_HOST, BAD_EVENT, UNSUPPORTED_LOG_STATE = 32, 33, 3
 MEM_HOST, MEM_DEVICE = 0, 1
 OPT_REQUIRE_FENCED_TIMEOUTS = 1
 OPT_AUTO_INDEX_BASE = 2              # (ABI 6) window W of the automatic index bases, 0 = off; 2^28 recommended (include/raftgpu.h)
+OPT_COMPACT_ANY_CLUSTER = 3          # 1: the compact formats and the ticks take clusters above MAX_COMPACT_CLUSTER nodes too (include/raftgpu.h); 0 = off
 NUM_COUNTERS = 8
 
 HEAD_DT = np.dtype([("hdr", "<u4"), ("aux", "<u4")])

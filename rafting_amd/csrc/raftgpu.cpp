@@ -66,6 +66,7 @@ struct rg_table {
     int require_fence = 0;                      // rg_table_option(RG_OPT_REQUIRE_FENCED_TIMEOUTS)
     int has_bases = 0;                          // rg_index_base_set has stored a non-zero base at some time (or RG_OPT_AUTO_INDEX_BASE was switched on)
     int auto_window = 0;                        // rg_table_option(RG_OPT_AUTO_INDEX_BASE): 0 = off
+    int compact_any_cluster = 0;                // rg_table_option(RG_OPT_COMPACT_ANY_CLUSTER): the compact formats and the ticks take a cluster above RG_MAX_COMPACT_CLUSTER
     Staging st_abcd32, st_terms32, st_out32, st_persist32;
     int lanes = -1;                             // -1: pick per launch; 0: split kernel; 64: single-wavefront kernel (RG_SPLIT env forces one)
     uint32_t simds = 1024;                      // SIMDs of the device (CUs x 4)
@@ -177,6 +178,11 @@ int rg_table_option(rg_table_t *t, int option, int value)
         if (t->auto_window != value) t->config_gen += 1;                // (the window is baked into a recorded launch like every option)
         if (value != 0 && !t->has_bases) t->has_bases = 1;              // (the kernels read the base column from now on)
         t->auto_window = value;
+        return 0;
+    case RG_OPT_COMPACT_ANY_CLUSTER:
+        if (value != 0 && value != 1) return fail(t, -1, "rg_table_option: RG_OPT_COMPACT_ANY_CLUSTER takes 0 or 1 (%d given)", value);
+        if (t->compact_any_cluster != value) t->config_gen += 1;        // (a tick recorded under one setting does not launch under the other)
+        t->compact_any_cluster = value;
         return 0;
     default: return fail(t, -1, "rg_table_option: unknown option %d", option);
     }
@@ -481,11 +487,12 @@ static int launch(rg_table *t, const rg::StepParams &p, bool sparse)
     return 0;
 }
 
-// the compact formats belong to clusters of up to RG_MAX_COMPACT_CLUSTER nodes (include/raftgpu.h)
+// the compact formats and the ticks belong to clusters of up to RG_MAX_COMPACT_CLUSTER nodes, or to a table with RG_OPT_COMPACT_ANY_CLUSTER (include/raftgpu.h)
 static int compact_ok(rg_table *t, const char *who)
 {
-    if (t->P > RG_MAX_COMPACT_CLUSTER)
-        return fail(t, -1, "%s: a cluster of %u nodes is decided on wide rows (rg_submit, rg_submit_async); the compact formats end at %d nodes", who, t->P, RG_MAX_COMPACT_CLUSTER);
+    if (t->P > RG_MAX_COMPACT_CLUSTER && !t->compact_any_cluster)
+        return fail(t, -1, "%s: a cluster of %u nodes is decided on wide rows (rg_submit, rg_submit_async); the compact formats end at %d nodes unless the table has "
+                           "RG_OPT_COMPACT_ANY_CLUSTER (rg_table_option), which lifts the limit", who, t->P, RG_MAX_COMPACT_CLUSTER);
     return 0;
 }
 

@@ -158,6 +158,7 @@ __global__ __launch_bounds__(256) void replicate_kernel(const ReplicateParams p)
     replicate_wave<F>(p, stage[wave], blockIdx.x * blockDim.x + wave * 64u, lane, p.count);
 }
 
+#ifdef RG_TU_MAIN                   // (rg_step.hpp, "translation units": what is not a template is compiled once)
 hipError_t launch_replicate(const ReplicateParams &p, int followers, hipStream_t s)
 {
     const uint32_t blocks = (p.count + 255) / 256;
@@ -176,6 +177,7 @@ hipError_t launch_replicate(const ReplicateParams &p, int followers, hipStream_t
     }
     return hipGetLastError();
 }
+#endif
 
 // ---- N4: timers ------------------------------------------------------------------------------------------
 __host__ __device__ __forceinline__ uint64_t timer_mix(uint64_t x)
@@ -203,6 +205,7 @@ __device__ __forceinline__ int64_t rearm(const TimerParams &p, int64_t d, uint32
 
 template <class P> __device__ __forceinline__ int64_t now_of(const P &p, uint32_t r) { return p.now_mem ? p.now_mem[r] : p.now[r]; }
 
+#ifdef RG_TU_MAIN
 __global__ __launch_bounds__(256) void timers_update_kernel(const TimerParams p)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -301,6 +304,7 @@ __global__ __launch_bounds__(256) void timers_emit_kernel(int64_t *deadline, con
         deadline[g] = -1;
     }
 }
+#endif
 
 // ---- the device-resident tick, folded (rg_tick2) ---------------------------------------------------------------------------------------------
 // A single-round tick over 65 536 groups is launch-bound, so what follows the decisions is folded: per group the batch's flags into the deadline
@@ -443,6 +447,7 @@ __device__ __forceinline__ void expire_tail(const TickFoldParams &p, const int64
     expire_tail(p, *p.now_last, d, g, holds, active, part);
 }
 
+#ifdef RG_TU_MAIN
 __global__ __launch_bounds__(256) void tick_fold_kernel(const TickFoldParams p)
 {
     __shared__ uint32_t part[136];
@@ -524,6 +529,7 @@ __global__ __launch_bounds__(256) void health_failure_kernel(const HealthParams 
     if (flags[i] & 1u) atomicAdd(&p.recent[at], 1);                              // unreachable (rows may repeat a (group, follower))
     if (flags[i] & 2u) atomicAdd(&p.t.peer_m[at].rejection, 1);                  // reject
 }
+#endif
 
 // Leader.isReady: ready = 1; for every State that isReady(...): ++ready > followers/2 -> true
 __device__ __forceinline__ uint8_t ready_of(const HealthParams &p, const int64_t now, const int32_t critical_point, const int64_t cool_down, const uint32_t g)
@@ -545,6 +551,7 @@ __device__ __forceinline__ uint8_t ready_of(const HealthParams &p, const int64_t
     }
     return out;
 }
+#ifdef RG_TU_MAIN
 __global__ __launch_bounds__(256) void ready_kernel(const HealthParams p, int64_t now, int32_t critical_point, int64_t cool_down, uint8_t *ready)
 {
     if (p.now_mem) now = *p.now_mem;
@@ -552,6 +559,7 @@ __global__ __launch_bounds__(256) void ready_kernel(const HealthParams p, int64_
     if (g >= p.t.groups) return;
     ready[g] = ready_of(p, now, critical_point, cool_down, g);
 }
+#endif
 
 // ---- the tail of a recorded tick (rg_tick2): timers + health, the leaders' sends, isReady and the fired tickets of every group in ONE launch ------------
 // A single-round tick is launch-bound (four graph nodes: 56 us for ~10 us of work at 65 536 groups), and the three steps after the decisions have the same
@@ -606,6 +614,33 @@ __global__ __launch_bounds__(2 * BLOCK) __attribute__((amdgpu_waves_per_eu(WAVES
     if (!holds && tp.ready != nullptr && in_table) tp.ready[g] = ready_of(tp.rp, *tp.rp.now_mem, tp.critical_point, tp.cool_down, g);
     if (tp.fp.expire) expire_tail(tp.fp, d, g, holds, active, part);
 }
+// 7 .. 14 followers (a table with RG_OPT_COMPACT_ANY_CLUSTER): one register budget, as for the step kernels (rg_step.hpp: launch_compact_big), and launchers over
+// a range of four follower counts that may have a translation unit of their own (rg_step.hpp, "translation units"); F = 0: not in this build
+template <int F>
+static hipError_t launch_tick_big(const StepParams &p, const TickTailParams &tp, const dim3 grid, hipStream_t s)
+{
+    if constexpr (F == 0) return hipErrorInvalidValue;
+    else { hipLaunchKernelGGL((tick_kernel<F, 1>), grid, dim3(2 * BLOCK), 0, s, p, tp); return hipGetLastError(); }
+}
+template <int LO>
+hipError_t launch_tick_range(const StepParams &p, const TickTailParams &tp, int followers, const dim3 grid, hipStream_t s)
+{
+    switch (followers - LO) {
+    case 0: return launch_tick_big<RG_BIG_F(LO)>(p, tp, grid, s);
+    case 1: return launch_tick_big<RG_BIG_F(LO + 1)>(p, tp, grid, s);
+    case 2: return launch_tick_big<RG_BIG_F(LO + 2)>(p, tp, grid, s);
+    case 3: return launch_tick_big<RG_BIG_F(LO + 3)>(p, tp, grid, s);
+    default: return hipErrorInvalidValue;
+    }
+}
+#define RG_TICK_RANGE(LO_) hipError_t launch_tick_range<LO_>(const StepParams &, const TickTailParams &, int, const dim3, hipStream_t)
+#if defined(RG_TU) && RG_TU == 1
+extern template RG_TICK_RANGE(7); extern template RG_TICK_RANGE(11);
+#elif defined(RG_TU)
+template RG_TICK_RANGE(RG_TU);
+#endif
+#undef RG_TICK_RANGE
+#ifdef RG_TU_MAIN
 hipError_t launch_tick(const StepParams &p, const TickTailParams &tp, int followers, hipStream_t s)
 {
     const uint32_t blocks = (p.count + BLOCK - 1) / BLOCK;
@@ -617,10 +652,13 @@ hipError_t launch_tick(const StepParams &p, const TickTailParams &tp, int follow
 #define RG_TICK_CASE(F_) case F_: if (many) hipLaunchKernelGGL((tick_kernel<F_, 4>), grid, wg, 0, s, p, tp); else hipLaunchKernelGGL((tick_kernel<F_, 1>), grid, wg, 0, s, p, tp); break;
     RG_TICK_CASE(1) RG_TICK_CASE(2) RG_TICK_CASE(3) RG_TICK_CASE(4) RG_TICK_CASE(5) RG_TICK_CASE(6)
 #undef RG_TICK_CASE
+    case 7: case 8: case 9: case 10: return launch_tick_range<7>(p, tp, followers, grid, s);
+    case 11: case 12: case 13: case 14: return launch_tick_range<11>(p, tp, followers, grid, s);
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }
+#endif
 // ---- the SPARSE recorded tick (rg_tick2_create_sparse): the same for a LIST of groups whose length changes from run to run --------------------------------
 // Most groups of a 100-us tick have no event, and tick_kernel reads and writes all of them all the same. Here a workgroup is 64 ROWS: row i of every per-row
 // column belongs to group gid[i], the columns are sized for p0.count = the tick's capacity, and the rows of THIS run — n = min(*rows_now, capacity) — are read
@@ -667,6 +705,52 @@ __global__ __launch_bounds__(2 * BLOCK) __attribute__((amdgpu_waves_per_eu(WAVES
     __syncthreads();
     if (!holds && tp.ready != nullptr && in_list) tp.ready[row] = ready_of(tp.rp, tp.fp.tp.now_mem[depth - 1u], tp.critical_point, tp.cool_down, g);
 }
+template <int F>
+static hipError_t launch_tick_sparse_big(const StepParams &p, const TickTailParams &tp, const uint32_t *rows_now, const dim3 grid, hipStream_t s)
+{
+    if constexpr (F == 0) return hipErrorInvalidValue;
+    else { hipLaunchKernelGGL((tick_sparse_kernel<F, 1>), grid, dim3(2 * BLOCK), 0, s, p, tp, rows_now); return hipGetLastError(); }
+}
+template <int F>
+static hipError_t launch_tick_tail_big(const TickTailParams &p, const dim3 grid, hipStream_t s)
+{
+    if constexpr (F == 0) return hipErrorInvalidValue;
+    else { hipLaunchKernelGGL(tick_tail_kernel<F>, grid, dim3(256), 0, s, p); return hipGetLastError(); }
+}
+template <int LO>
+hipError_t launch_tick_sparse_range(const StepParams &p, const TickTailParams &tp, const uint32_t *rows_now, int followers, const dim3 grid, hipStream_t s)
+{
+    switch (followers - LO) {
+    case 0: return launch_tick_sparse_big<RG_BIG_F(LO)>(p, tp, rows_now, grid, s);
+    case 1: return launch_tick_sparse_big<RG_BIG_F(LO + 1)>(p, tp, rows_now, grid, s);
+    case 2: return launch_tick_sparse_big<RG_BIG_F(LO + 2)>(p, tp, rows_now, grid, s);
+    case 3: return launch_tick_sparse_big<RG_BIG_F(LO + 3)>(p, tp, rows_now, grid, s);
+    default: return hipErrorInvalidValue;
+    }
+}
+template <int LO>
+hipError_t launch_tick_tail_range(const TickTailParams &p, int followers, const dim3 grid, hipStream_t s)
+{
+    switch (followers - LO) {
+    case 0: return launch_tick_tail_big<RG_BIG_F(LO)>(p, grid, s);
+    case 1: return launch_tick_tail_big<RG_BIG_F(LO + 1)>(p, grid, s);
+    case 2: return launch_tick_tail_big<RG_BIG_F(LO + 2)>(p, grid, s);
+    case 3: return launch_tick_tail_big<RG_BIG_F(LO + 3)>(p, grid, s);
+    default: return hipErrorInvalidValue;
+    }
+}
+#define RG_SPARSE_RANGE(LO_) hipError_t launch_tick_sparse_range<LO_>(const StepParams &, const TickTailParams &, const uint32_t *, int, const dim3, hipStream_t)
+#define RG_TAIL_RANGE(LO_) hipError_t launch_tick_tail_range<LO_>(const TickTailParams &, int, const dim3, hipStream_t)
+#if defined(RG_TU) && RG_TU == 1
+extern template RG_SPARSE_RANGE(7); extern template RG_SPARSE_RANGE(11);
+extern template RG_TAIL_RANGE(7); extern template RG_TAIL_RANGE(11);
+#elif defined(RG_TU)
+template RG_SPARSE_RANGE(RG_TU);
+template RG_TAIL_RANGE(RG_TU);
+#endif
+#undef RG_SPARSE_RANGE
+#undef RG_TAIL_RANGE
+#ifdef RG_TU_MAIN
 // the fired tickets of the whole table at the clock of the run's last round, now[R - 1], one lane per group: the sparse tick's second node (expire_tail as the dense kernels call it)
 __global__ __launch_bounds__(256) void tick_expire_kernel(const TickFoldParams p)
 {
@@ -687,6 +771,8 @@ hipError_t launch_tick_sparse(const StepParams &p, const TickTailParams &tp, con
 #define RG_TICK_CASE(F_) case F_: if (many) hipLaunchKernelGGL((tick_sparse_kernel<F_, 4>), grid, wg, 0, s, p, tp, rows_now); else hipLaunchKernelGGL((tick_sparse_kernel<F_, 1>), grid, wg, 0, s, p, tp, rows_now); break;
     RG_TICK_CASE(1) RG_TICK_CASE(2) RG_TICK_CASE(3) RG_TICK_CASE(4) RG_TICK_CASE(5) RG_TICK_CASE(6)
 #undef RG_TICK_CASE
+    case 7: case 8: case 9: case 10: return launch_tick_sparse_range<7>(p, tp, rows_now, followers, grid, s);
+    case 11: case 12: case 13: case 14: return launch_tick_sparse_range<11>(p, tp, rows_now, followers, grid, s);
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -705,6 +791,8 @@ hipError_t launch_tick_tail(const TickTailParams &p, int followers, hipStream_t 
 #define RG_TAIL_CASE(F_) case F_: hipLaunchKernelGGL(tick_tail_kernel<F_>, dim3(blocks), dim3(256), 0, s, p); break;
     RG_TAIL_CASE(1) RG_TAIL_CASE(2) RG_TAIL_CASE(3) RG_TAIL_CASE(4) RG_TAIL_CASE(5) RG_TAIL_CASE(6)
 #undef RG_TAIL_CASE
+    case 7: case 8: case 9: case 10: return launch_tick_tail_range<7>(p, followers, dim3(blocks), s);
+    case 11: case 12: case 13: case 14: return launch_tick_tail_range<11>(p, followers, dim3(blocks), s);
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -807,5 +895,7 @@ hipError_t launch_copy(const void *src, void *dst, size_t bytes, hipStream_t s)
     hipLaunchKernelGGL(copy_kernel, dim3(2048), dim3(256), 0, s, (const u32x4 *)src, (u32x4 *)dst, bytes / 16);
     return hipGetLastError();
 }
+
+#endif
 
 }  // namespace rg

@@ -747,6 +747,8 @@ struct Row32 { U32x2 h; I32x4 q; };
 // (class_word). header' is the header as loaded, with KIND_OUT_OF_DOMAIN when a field leaves [0, EV_LIMIT) — `aux` too where it is a role
 // epoch (acks, vote replies, timeouts) or the entries' term: such a row has no class and sends the workgroup to the 64-bit body.
 constexpr int CW_AUXC = 18;         // table only: aux of this kind is a role epoch (it must be in the domain)
+// F: the follower count of the kernel that fills the table (0: any) — above 6 followers the index is written masked to its four bits (rg_tier1n.hpp: cw_follower)
+template <int F = 0>
 __device__ __forceinline__ uint32_t class_entry(const StepParams &p, uint32_t idx)
 {
     const uint32_t kind = idx & 15u, slot = idx >> 4;
@@ -761,7 +763,8 @@ __device__ __forceinline__ uint32_t class_entry(const StepParams &p, uint32_t id
                          ((vrep & peer_ok) ? 1u << CW_VR : 0u) | ((kind == RG_EV_PV_REPLY) ? 1u << CW_PV : 0u) | ((kind == RG_EV_TIMEOUT) ? 1u << CW_TO : 0u) |
                          ((vreq & (slot < P)) ? 1u << CW_VQ : 0u) | ((kind == RG_EV_PV_REQ) ? 1u << CW_PVQ : 0u) | ((kind == RG_EV_NONE) ? 1u << CW_NONE : 0u) |
                          ((((0x1CCu >> kind) & 1u) != 0) ? 1u << CW_AUXC : 0u);              // kinds 2, 3, 6, 7, 8
-    return cls | (j << 10) | (slot << 5) | (31u - j);
+    const uint32_t j4 = F > 6 ? (j & 15u) : j;                        // (j <= 13 in any case: an ack's slot is below the cluster size)
+    return cls | (j4 << 10) | (slot << 5) | (31u - j);
 }
 // Per row, in sign words (rg_tier1n.hpp): AE stays only with prevLogTerm != 0 and no entries, or at most RG_MAX_AE_ENTRIES of one term;
 // CLIENT only with n >= 1; nothing stays when a field is out of the domain.
@@ -852,7 +855,7 @@ __device__ __forceinline__ bool narrow_body(const StepParams &p, unsigned char *
         };
         // the tables (only this wavefront reads them: no barrier needed, its own LDS operations are ordered)
 #pragma unroll
-        for (int k = 0; k < 4; k++) sh_lutc[lane + 64u * k] = class_entry(p, lane + 64u * k);
+        for (int k = 0; k < 4; k++) sh_lutc[lane + 64u * k] = class_entry<F>(p, lane + 64u * k);
 #pragma unroll
         for (int k = 0; k < 2; k++) {
             const uint32_t i7 = lane + 64u * k;
@@ -1289,18 +1292,80 @@ static hipError_t launch_f(const StepParams &p, bool sparse, int shape, hipStrea
     }
 }
 
-// clusters of 8 .. 15 nodes (ABI 5): the wide-row kernels only — the decision code is generic in F (the quorum select is an insertion network, the
-// follower records live in LDS), the compact-row kernels' LDS budget and class word are not
+// clusters of 8 .. 15 nodes: the wide-row kernels (ABI 5) and, for a table with RG_OPT_COMPACT_ANY_CLUSTER, the compact-row kernels — the decision code is generic
+// in F (the quorum select is an insertion network, the follower records live in LDS, the class word carries a 4-bit follower index: rg_tier1n.hpp). ONE register
+// budget (WAVES = 1: whatever the allocator wants) whatever the size of the launch: with 7 .. 14 followers' matchIndex values in registers the allocator asks for
+// 120 .. 202 VGPRs, so a 128-VGPR variant could only be had by spilling from 9 followers on, and the LDS (25 .. 38 KB per workgroup) caps a CU at four to six
+// workgroups anyway.
+template <int F>
+static hipError_t launch_compact_big(const StepParams &p, bool sparse, hipStream_t s)
+{
+    const uint32_t blocks = (p.count + BLOCK - 1) / BLOCK;
+    if (blocks == 0) return hipSuccess;
+    if (p.count >= (1u << 28)) return hipErrorInvalidValue;       // the I/O wavefront addresses a row as scalar base + 32-bit lane offset
+    const dim3 grid(blocks), wg(2 * BLOCK);
+    const bool out32 = p.out32 != nullptr;
+    if (p.force_wide != 0) {
+        if (out32) { if (sparse) hipLaunchKernelGGL((step32_wide_kernel<F, true, 1, true>), grid, wg, 0, s, p); else hipLaunchKernelGGL((step32_wide_kernel<F, false, 1, true>), grid, wg, 0, s, p); }
+        else       { if (sparse) hipLaunchKernelGGL((step32_wide_kernel<F, true, 1, false>), grid, wg, 0, s, p); else hipLaunchKernelGGL((step32_wide_kernel<F, false, 1, false>), grid, wg, 0, s, p); }
+    } else {
+        if (out32) { if (sparse) hipLaunchKernelGGL((step32_kernel<F, true, 1, true>), grid, wg, 0, s, p); else hipLaunchKernelGGL((step32_kernel<F, false, 1, true>), grid, wg, 0, s, p); }
+        else       { if (sparse) hipLaunchKernelGGL((step32_kernel<F, true, 1, false>), grid, wg, 0, s, p); else hipLaunchKernelGGL((step32_kernel<F, false, 1, false>), grid, wg, 0, s, p); }
+    }
+    return hipGetLastError();
+}
+
+// Which of the follower counts 7 .. 14 a build has kernels for (bit F of the mask): all of them, or — an analysis build with RG_BUILD_ONLY_F4 — none, or the
+// ones -DRG_BUILD_ALSO_F=<mask> names (tests/test_compact_large_cluster_static_cpu.py: (1 << 8) | (1 << 14)).
+#if !defined(RG_BUILD_ONLY_F4)
+#define RG_BIG_F_MASK 0x7F80u
+#elif defined(RG_BUILD_ALSO_F)
+#define RG_BIG_F_MASK (RG_BUILD_ALSO_F)
+#else
+#define RG_BIG_F_MASK 0u
+#endif
+#define RG_BIG_F(F_) ((((RG_BIG_F_MASK) >> (F_)) & 1u) ? (F_) : 0)      // F_ where the build has it, else 0: launch_big<0> and its like answer hipErrorInvalidValue
+
+// TRANSLATION UNITS. The kernels of 7 .. 14 followers are half of this file's compile time, and a translation unit is compiled by one thread. Their
+// launchers are therefore function templates over a RANGE of four follower counts (LO = 7: 7 .. 10, LO = 11: 11 .. 14) that a build may instantiate in
+// translation units of their own: the Makefile compiles rg_kernels.hip three times — -DRG_TU=1: everything else, the ranges declared `extern template`;
+// -DRG_TU=7 and -DRG_TU=11: one range each and nothing that is not a template — side by side. Without RG_TU (the host emulation of tests/devemu, the analysis
+// builds) one translation unit holds everything, as before. A kernel is launched from the unit that holds it: no relocatable device code is needed.
+#if !defined(RG_TU) || RG_TU == 1
+#define RG_TU_MAIN 1                // this unit holds what is not a template: the kernels and launchers without a follower count, and the public launch_* entry points
+#endif
+
 template <int F>
 static hipError_t launch_big(const StepParams &p, bool sparse, int shape, hipStream_t s)
 {
-    switch (shape) {
+    if constexpr (F == 0) return hipErrorInvalidValue;
+    else switch (shape) {
     case 0:  return launch_split<F>(p, sparse, s);
     case 64: return launch_single<F>(p, sparse, s);
+    case 32: return launch_compact_big<F>(p, sparse, s);
     default: return hipErrorInvalidValue;
     }
 }
+template <int LO>
+hipError_t launch_step_range(const StepParams &p, int followers, bool sparse, int shape, hipStream_t s)
+{
+    switch (followers - LO) {
+    case 0: return launch_big<RG_BIG_F(LO)>(p, sparse, shape, s);
+    case 1: return launch_big<RG_BIG_F(LO + 1)>(p, sparse, shape, s);
+    case 2: return launch_big<RG_BIG_F(LO + 2)>(p, sparse, shape, s);
+    case 3: return launch_big<RG_BIG_F(LO + 3)>(p, sparse, shape, s);
+    default: return hipErrorInvalidValue;
+    }
+}
+#define RG_STEP_RANGE(LO_) hipError_t launch_step_range<LO_>(const StepParams &, int, bool, int, hipStream_t)
+#if defined(RG_TU) && RG_TU == 1
+extern template RG_STEP_RANGE(7); extern template RG_STEP_RANGE(11);
+#elif defined(RG_TU)
+template RG_STEP_RANGE(RG_TU);
+#endif
+#undef RG_STEP_RANGE
 
+#ifdef RG_TU_MAIN
 hipError_t launch_step(const StepParams &p, int followers, bool sparse, int shape, hipStream_t s)
 {
     switch (followers) {
@@ -1310,18 +1375,13 @@ hipError_t launch_step(const StepParams &p, int followers, bool sparse, int shap
     case 3: return launch_f<3>(p, sparse, shape, s);
     case 5: return launch_f<5>(p, sparse, shape, s);
     case 6: return launch_f<6>(p, sparse, shape, s);
-    case 7: return launch_big<7>(p, sparse, shape, s);
-    case 8: return launch_big<8>(p, sparse, shape, s);
-    case 9: return launch_big<9>(p, sparse, shape, s);
-    case 10: return launch_big<10>(p, sparse, shape, s);
-    case 11: return launch_big<11>(p, sparse, shape, s);
-    case 12: return launch_big<12>(p, sparse, shape, s);
-    case 13: return launch_big<13>(p, sparse, shape, s);
-    case 14: return launch_big<14>(p, sparse, shape, s);
 #endif
     case 4: return launch_f<4>(p, sparse, shape, s);
+    case 7: case 8: case 9: case 10: return launch_step_range<7>(p, followers, sparse, shape, s);
+    case 11: case 12: case 13: case 14: return launch_step_range<11>(p, followers, sparse, shape, s);
     default: return hipErrorInvalidValue;
     }
 }
+#endif
 
 }  // namespace rg

@@ -34,8 +34,9 @@ __device__ __forceinline__ sw s_pos(int32_t x) { return (int32_t)(0u - (uint32_t
 __device__ __forceinline__ uint32_t push_bit(uint32_t acc, sw w) { return (acc << 1) | ((uint32_t)w >> 31); }              // v_alignbit_b32
 
 // ---- the class word of a row (made by the I/O wavefront: class_word() in rg_step.hpp) --------------------------------------
-// bit 31 .. 19: one bit per state-independent fact; 12..10: follower index j of an ack's responder (0 for every other row); 8..5: slot;
-// 4..0: 31 - j (the shift that brings bit j of `pending` to the sign position)
+// bit 31 .. 19: one bit per state-independent fact; 13..10: follower index j of an ack's responder (0 for every other row; 0 .. 13: a 15-node cluster has
+// 14 followers. The kernels of up to 6 followers read bits 12..10 only, cw_follower<F>); 8..5: slot; 4..0: 31 - j (the shift that brings bit j of `pending` to
+// the sign position: 18 .. 31, `pending` holds one bit per follower in bits 13..0); bits 17..14 and 9 are free
 constexpr int CW_ACK = 31;          // AE_ACK from a remote peer
 constexpr int CW_AE = 30;           // HDR_AE_OK
 constexpr int CW_CLIENT = 29;       // CLIENT_APPEND with n >= 1
@@ -49,6 +50,8 @@ constexpr int CW_VQ = 22;           // RV_REQ / PV_REQ with slot < cluster
 constexpr int CW_PVQ = 21;          // PV_REQ
 constexpr int CW_NONE = 19;         // row not addressed this round
 __device__ __forceinline__ sw cw_bit(int32_t cw, int bit) { return (int32_t)((uint32_t)cw << (31 - bit)); }
+// the follower index of an ack's responder: three bits where the cluster has at most six followers (what these kernels have always read), four above that
+template <int F> __device__ __forceinline__ uint32_t cw_follower(int32_t cw) { return ((uint32_t)cw >> 10) & (F <= 6 ? 7u : 15u); }
 
 // ---- the predicate word of a decided row (expanded by the I/O wavefront: expand_predicates() below) -------------------------
 // main block, bits 6..0 (pushed in this order, so the first is the highest): fa_n, x_ct, conv, append, commit, fc_n, drop
@@ -168,7 +171,7 @@ __device__ __forceinline__ sw tier1n(const StepParams &p, GroupN &g, PeersNarrow
     const sw x_tl = s_ne(lt, term);                                 // the tail entry is not of currentTerm
     // The ack block's LDS reads are issued first and the AppendEntries block — which needs nothing from LDS — is placed between them and
     // their use: left to itself the scheduler opens the round with the ack block and a wait for the reads.
-    const uint32_t j = ((uint32_t)cw >> 10) & 7u;                   // follower index of an ack's responder, 0 for any other row
+    const uint32_t j = cw_follower<F>(cw);                           // follower index of an ack's responder, 0 for any other row
     const I32x4 st = pe.rec[j * BLOCK];
     int32_t m[F];
     pe.load_matches(m);
@@ -407,7 +410,7 @@ __device__ __forceinline__ bool tier15(const StepParams &p, GroupN &g, PeersNarr
     {
         const int32_t slot = (int32_t)(((uint32_t)cw >> 5) & 15u);
         // (i)
-        const uint32_t j = ((uint32_t)cw >> 10) & 7u;
+        const uint32_t j = cw_follower<F>(cw);
         const bool nack_shape = open & (cw_bit(cw, CW_ACK) < 0) & (cw_bit(cw, CW_FLAG) >= 0) & (g.stl_n >= 0) & (aux == (int32_t)g.role_epoch) & (a <= g.term);
         if (nack_shape) {
             const I32x4 st = pe.rec[j * BLOCK];

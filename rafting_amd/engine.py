@@ -703,6 +703,11 @@ class Table:
         max(base, a - window) from the next launch on (advance_index_base is the same rule for a host mirror); 0 switches it off"""
         self.set_option(abi.OPT_AUTO_INDEX_BASE, window)
 
+    def set_compact_any_cluster(self, on=True):
+        """rg_table_option(RG_OPT_COMPACT_ANY_CLUSTER): the compact formats (submit32*, PackedBatch, DeviceBatch32) and the ticks (Tick, Tick2) take this
+        table whatever its cluster size; off (the default) they refuse clusters above abi.MAX_COMPACT_CLUSTER nodes"""
+        self.set_option(abi.OPT_COMPACT_ANY_CLUSTER, 1 if on else 0)
+
     def set_option(self, option, value):
         """rg_table_option, e.g. (abi.OPT_REQUIRE_FENCED_TIMEOUTS, 1)"""
         self._check(lib().rg_table_option(self._h, option, int(value)))

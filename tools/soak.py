@@ -5,7 +5,8 @@ single-wavefront kernel, compact rows (rg_submit32: step32_kernel's 32-bit body)
 outcome rows (rg_submit32c).
 usage: python tools/soak.py [seconds=240] [routes, comma separated: default all six]
 RG_SOAK_SEED=n starts the seeds at n instead of 1000 (a second soak that repeats the first one's seeds adds nothing); RG_SOAK_BIG=1 adds clusters of 8 .. 15
-nodes to the shapes, on the wide-row routes only (the compact formats refuse them)."""
+nodes to the shapes, on the wide-row routes only (the compact formats refuse them) — unless --compact-any-cluster is given (anywhere on the command line): every
+table then gets RG_OPT_COMPACT_ANY_CLUSTER, the compact routes take every cluster size, and RG_SOAK_BIG=1 puts the large clusters on every route."""
 import os
 import sys
 import time
@@ -18,16 +19,29 @@ from rafting_amd import abi, engine  # noqa: E402
 from tests import test_gpu_parity as T  # noqa: E402
 
 WIDE_SUBMIT = engine.Table.submit
+ANY_CLUSTER = "--compact-any-cluster" in sys.argv
+if ANY_CLUSTER:
+    sys.argv.remove("--compact-any-cluster")
+    _INIT = engine.Table.__init__
+
+    def _init_with_option(self, *a, **kw):
+        _INIT(self, *a, **kw)
+        self.set_compact_any_cluster(True)
+    engine.Table.__init__ = _init_with_option
+
+
+def compact_route_takes(table):
+    return ANY_CLUSTER or table.cluster <= abi.MAX_COMPACT_CLUSTER
 
 
 def compact_submit(self, batch, out=None, fill=0):      # what tests/test_gpu_parity.py::route_through_compact installs
-    if batch.hint is None and abi.batch_fits_32(batch) and self.cluster <= abi.MAX_COMPACT_CLUSTER:
+    if batch.hint is None and abi.batch_fits_32(batch) and compact_route_takes(self):
         return self.submit32(batch, out, fill)
     return WIDE_SUBMIT(self, batch, out, fill)
 
 
 def out32_submit(self, batch, out=None, fill=0):        # route_through_compact(out32=True): rg_submit32c + rg_outcome32_unpack, the raw rows held to their contract
-    if batch.hint is None and abi.batch_fits_32(batch) and batch.gid is None and self.cluster <= abi.MAX_COMPACT_CLUSTER:
+    if batch.hint is None and abi.batch_fits_32(batch) and batch.gid is None and compact_route_takes(self):
         before = self.read_state()
         raw = self.submit32c(batch, fill=fill)
         got, _ = engine.unpack32(raw, batch.rounds, batch.count, before.role_epoch)
@@ -55,7 +69,7 @@ def main():
         pre_vote = (runs // len(shapes)) % 2 == 0
         os.environ["RG_FAST"] = "0" if runs % 5 == 4 else "1"
         route = routes[(runs // 3) % len(routes)]
-        if big and route in ("split", "single") and runs % 3 == 2:       # every third run of a wide-row route: a cluster above seven nodes
+        if big and (ANY_CLUSTER or route in ("split", "single")) and runs % 3 == 2:       # every third run of a wide-row route (of every route with --compact-any-cluster): a cluster above seven nodes
             cluster, self_slot = big[big_runs % len(big)]
             big_runs += 1
         os.environ["RG_SPLIT"] = "0" if route == "single" else "1"
