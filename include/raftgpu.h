@@ -680,6 +680,68 @@ int rg_tick2_launch(rg_tick2_t *tick);      /* asynchronous on the table's strea
 int rg_tick2_wait(rg_tick2_t *tick);
 int rg_tick2_destroy(rg_tick2_t *tick);
 
+/* ---- ASSEMBLING A BATCH ON THE DEVICE (new symbols only; the ABI stays 6) -----------------------------------------------------------------
+ * rg_submit32c_sparse_rounds and the sparse tick with a depth take ONE shape: a strictly ascending gid list, n and R, rows laid out [round][capacity], the k-th
+ * queued event of a group in round k. A host receives events in ARRIVAL ORDER, for arbitrary groups, from many reader threads; and the tickets a tick listed in
+ * expired_gid / expired_epoch / expired_count want one RG_EV_TIMEOUT row each in the next tick. rg_assemble32 turns the one into the other on the device: a reader
+ * thread's whole job is to append (gid, head, abcd) to an arrival log, and a fired ticket gets its row without the host reading the list.
+ *
+ * THE SEQUENCE S of a run is the expired source first, then the arrival log:
+ *   - entries j = 0 .. e - 1 of the expired source, e = min(*expired_count, expired_capacity); e = 0 when the source is absent (all three pointers NULL) and when
+ *     *expired_count is 0xFFFFFFFF — the tick's mark for a look-back that ran into its bound, whose list is not to be used. Entry j becomes the row
+ *     head = {RG_HDR_MAKE(RG_EV_TIMEOUT, 0, 0, 0), expired_epoch[j]} (the fenced onTimeout), abcd = {0, 0, 0, 0}, with the id 0x80000000 | j;
+ *   - then the arrival events k = 0 .. m - 1, m = min(*count, capacity), with the id k. (A ticket fired at the END of the previous tick: its onTimeout precedes
+ *     what has arrived since.)
+ * An event whose gid is at or above the table's group count is counted in stats[2] and otherwise ignored, in both memspaces: the log is never trusted.
+ *
+ * THE RESULT. Let U be the ascending set of the distinct valid gids in S. n = min(|U|, C), C = out->capacity; gid[0 .. n) holds the n smallest gids of U. The events of
+ * group gid[i], in S order, occupy rounds 0, 1, 2, .. of row i, packed from round 0 with no holes; those of rank >= D (D = out->max_rounds) are DEFERRED, and so is every
+ * event of a group outside the list. R = the greatest number of rounds any listed row uses, 1 when n = 0. *count = n, *rounds = R. head / abcd / origin are [D][C]: row i
+ * of round r at r * C + i — the stride is the capacity, as for the tick. A cell (r, i), r < R and i < n, that holds an event gets the event's head and abcd VERBATIM and
+ * origin = its id; one that holds none gets head = {0, 0} (RG_EV_NONE), abcd = {0, 0, 0, 0}, origin = 0xFFFFFFFF. Rows >= n of any round and rounds >= R are NOT
+ * TOUCHED in any column: the tick's own convention. deferred[] receives the deferred ids in S order, the first deferred_capacity of them; stats = {events placed,
+ * events deferred (may exceed deferred_capacity), events with gid >= groups, 0}. A host puts the deferred events at the HEAD of its next arrival log (a deferred
+ * ticket as a plain RG_EV_TIMEOUT row with the epoch it was listed with): per-group order then survives any overflow. `origin` routes outcome row (r, i) of the
+ * launch that decides the batch back to the event it answers.
+ * Every output is a function of the inputs alone, bit for bit, run after run: slots are claimed through atomics, ranks come from the ids.
+ *
+ * INDEX BASES: nothing is done and nothing needs doing. Rows are moved verbatim, so their indices stay relative to the bases of the launch that will decide them
+ * (rg_batch32_pack_rel on the reader's side, as for any compact row); `aux` of an AppendEntries row still addresses the entry_terms array handed to that launch.
+ *
+ * MEMSPACES. RG_MEM_DEVICE: every pointer of both structs is device-visible (rg_dev_alloc / rg_host_alloc) and stays valid until the run has executed; the call is
+ * asynchronous on the table's stream, synchronises nothing and decides nothing on the host from device data — its grids are sized from the capacities and leave
+ * early on the counts they read when they run (the counts and the entries below them stand still from the call until the run has executed; a reader may append BEYOND *count). So a run can be followed on the same stream by rg_tick2_launch of a recording made over the very same gid / count /
+ * rounds / head / abcd buffers (rg_tick2_create_sparse_rounds with capacity C and io->rounds D), with the previous tick's expired_* columns as the second source: the
+ * host knows neither n nor R. RG_MEM_HOST: host arrays, staged in and out, synchronous, after the pipeline has drained like every other entry point.
+ * The assembler owns the scratch of its runs (about 8 bytes per group and 9 per event) and belongs to its table: destroy it before the table; one run at a time.
+ * Refused (-1, with a message, before any launch): a missing column (deferred may be NULL with deferred_capacity 0), C = 0 or above the group count, D outside
+ * 1 .. 64, an arrival or expired capacity above what the assembler was created for, an expired source given in part, an unknown memspace and, in RG_MEM_DEVICE, a
+ * pointer that is neither device memory nor page-locked host memory. */
+typedef struct {                       /* the arrival log of one run */
+    const uint32_t       *count;       /* [1] events of THIS run, m = min(*count, capacity); read when the run executes */
+    uint32_t              capacity;    /* what gid / head / abcd hold */
+    const uint32_t       *gid;         /* [capacity] group of event k, ANY order, repeats allowed */
+    const rg_ev_head_t   *head;        /* [capacity] compact rows exactly as rg_batch32_t carries them */
+    const rg_ev_quad32_t *abcd;        /* [capacity] */
+    const uint32_t       *expired_gid, *expired_epoch, *expired_count;   /* optional second source: the columns a tick wrote; all three or none */
+    uint32_t              expired_capacity;
+} rg_arrivals_t;
+typedef struct {                       /* the columns rg_submit32c_sparse_rounds / rg_tick2_rounds_t + rg_tick2_io_t read, plus routing */
+    uint32_t        capacity;          /* C: rows the per-row columns hold, 1 .. groups */
+    uint32_t        max_rounds;        /* D: 1 .. 64 */
+    uint32_t       *gid, *count, *rounds;         /* [C], [1] = n, [1] = R */
+    rg_ev_head_t   *head;              /* [D][C] */
+    rg_ev_quad32_t *abcd;              /* [D][C] */
+    uint32_t       *origin;            /* [D][C] the id of the event a cell holds, 0xFFFFFFFF for none */
+    uint32_t       *deferred;          /* [deferred_capacity] ids of the events that did not fit, in S order */
+    uint32_t        deferred_capacity;
+    uint32_t       *stats;             /* [4] */
+} rg_assembled_t;
+typedef struct rg_assembler rg_assembler_t;
+int rg_assembler_create(rg_table_t *t, uint32_t max_events, uint32_t max_expired, rg_assembler_t **a);
+int rg_assemble32(rg_assembler_t *a, const rg_arrivals_t *in, const rg_assembled_t *out, int memspace);
+int rg_assembler_destroy(rg_assembler_t *a);
+
 /* ---- device memory helpers (so a host without its own HIP binding can keep batches in HBM) --- */
 /* Page-locked host memory for RG_MEM_HOST batches (JNI: wrap it with NewDirectByteBuffer): staging then runs at PCIe
  * speed instead of through the driver's pageable bounce buffers. */

@@ -130,6 +130,21 @@ class CTick2Rounds(C.Structure):       # rg_tick2_rounds_t
     _fields_ = [("gid", C.c_void_p), ("count", C.c_void_p), ("rounds", C.c_void_p), ("capacity", C.c_uint32)]
 
 
+class CArrivals(C.Structure):          # rg_arrivals_t
+    _fields_ = [("count", C.c_void_p), ("capacity", C.c_uint32), ("gid", C.c_void_p), ("head", C.c_void_p), ("abcd", C.c_void_p),
+                ("expired_gid", C.c_void_p), ("expired_epoch", C.c_void_p), ("expired_count", C.c_void_p), ("expired_capacity", C.c_uint32)]
+
+
+class CAssembled(C.Structure):         # rg_assembled_t
+    _fields_ = [("capacity", C.c_uint32), ("max_rounds", C.c_uint32), ("gid", C.c_void_p), ("count", C.c_void_p), ("rounds", C.c_void_p),
+                ("head", C.c_void_p), ("abcd", C.c_void_p), ("origin", C.c_void_p), ("deferred", C.c_void_p), ("deferred_capacity", C.c_uint32),
+                ("stats", C.c_void_p)]
+
+
+ORIGIN_NONE, ORIGIN_EXPIRED = 0xFFFFFFFF, 0x80000000      # rg_assembled_t.origin: no event in the cell / bit 31 of the id of an entry of the expired source
+EXPIRED_UNTRUSTED = 0xFFFFFFFF                            # *expired_count of a tick whose look-back ran into its bound
+
+
 _STATE_FIELDS = [
     ("current_term", np.int64, 1),
     ("voted_for", np.int32, 1),

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "rg_device.hpp"
+#include "rg_assemble.hpp"
 
 namespace rg {
 hipError_t launch_step(const StepParams &p, int followers, bool sparse, int shape, hipStream_t s);
@@ -84,6 +85,7 @@ struct rg_table {
     uint64_t config_gen = 0;                    // bumped by whatever changes what a recorded launch has baked in (options, the first index base)
     std::vector<struct rg_tick *> ticks;        // live recordings: invalidated when the table goes
     std::vector<struct rg_tick2 *> ticks2;
+    std::vector<struct rg_assembler *> assemblers;   // live assemblers (rg_assembler_create): their scratch goes with the table
     uint32_t *timer_counts = nullptr;           // [waves + 1]: per-wave counts / offsets, last = total
     int64_t election_ms = 900, heartbeat_ms = 300;   // raft1.xml:10-13
     uint64_t timer_seed = 0;
@@ -190,6 +192,7 @@ int rg_table_option(rg_table_t *t, int option, int value)
 
 static void tick_release(struct rg_tick *k);
 static void tick2_release(struct rg_tick2 *k);
+static void assembler_release(struct rg_assembler *a);
 
 int rg_table_destroy(rg_table_t *t)
 {
@@ -199,7 +202,8 @@ int rg_table_destroy(rg_table_t *t)
     // recordings that outlive their table keep no pointer into it: their launch / wait fail with -1, their destroy only frees the handle
     for (struct rg_tick *k : t->ticks) tick_release(k);
     for (struct rg_tick2 *k : t->ticks2) tick2_release(k);
-    t->ticks.clear(); t->ticks2.clear();
+    for (struct rg_assembler *a : t->assemblers) assembler_release(a);
+    t->ticks.clear(); t->ticks2.clear(); t->assemblers.clear();
     void *cols[] = {t->dt.term_commit, t->dt.epoch, t->dt.window, t->dt.ident, t->dt.elect, t->dt.runs,
                     t->dt.peer_en, t->dt.peer_m, t->dt.ibase, t->wide_bodies, t->counters, t->st_gid.ptr, t->st_head.ptr, t->st_ab.ptr,
                     t->st_cd.ptr, t->st_hint.ptr, t->st_terms.ptr, t->st_reply.ptr, t->st_logfx.ptr,
@@ -1015,6 +1019,183 @@ int rg_tick2_wait(rg_tick2_t *k)
     HIP_TRY(t, hipSetDevice(t->device));
     HIP_TRY(t, hipStreamSynchronize(t->stream));
     k->in_flight = false;
+    return 0;
+}
+
+/* ---- assembling a batch on the device (rg_assemble32; kernels: rg_assemble.hpp) ------------------------------------------------------ */
+struct rg_assembler {
+    rg_table *t = nullptr;
+    uint32_t max_events = 0, max_expired = 0;
+    rg::AsmParams sc{};                             // the scratch pointers and their capacities; the rest is filled per run
+    Staging in_words, in_gid, in_head, in_abcd, ex_gid, ex_epoch;                       // RG_MEM_HOST: the sources ...
+    Staging out_gid, out_words, out_head, out_abcd, out_origin, out_deferred;           // ... and the batch
+};
+
+static void assembler_release(struct rg_assembler *a)
+{
+    void *cols[] = {a->sc.cnt, a->sc.bitmap, a->sc.rowof, a->sc.wordoff, a->sc.rowcnt, a->sc.segoff, a->sc.seg, a->sc.flag, a->sc.dcounts, a->sc.big, a->sc.scalars,
+                    a->in_words.ptr, a->in_gid.ptr, a->in_head.ptr, a->in_abcd.ptr, a->ex_gid.ptr, a->ex_epoch.ptr,
+                    a->out_gid.ptr, a->out_words.ptr, a->out_head.ptr, a->out_abcd.ptr, a->out_origin.ptr, a->out_deferred.ptr};
+    for (void *c : cols) if (c) (void)hipFree(c);
+    *a = rg_assembler{};
+}
+
+int rg_assembler_destroy(rg_assembler_t *a)
+{
+    if (!a) return 0;
+    if (rg_table *t = a->t) {
+        (void)hipSetDevice(t->device);
+        if (t->stream) (void)hipStreamSynchronize(t->stream);
+        t->assemblers.erase(std::remove(t->assemblers.begin(), t->assemblers.end(), a), t->assemblers.end());
+        assembler_release(a);
+    }
+    delete a;
+    return 0;
+}
+
+int rg_assembler_create(rg_table_t *t, uint32_t max_events, uint32_t max_expired, rg_assembler_t **out)
+{
+    if (!t) return -1;
+    if (!out) return fail(t, -1, "rg_assembler_create: a is NULL");
+    *out = nullptr;
+    if ((uint64_t)max_events + max_expired >= (1ull << 31))
+        return fail(t, -1, "rg_assembler_create: %u + %u events: a run holds fewer than 2^31 (the ids of the expired source carry bit 31)", max_events, max_expired);
+    if (bind(t)) return -2;
+    rg_assembler *a = new rg_assembler();
+    a->t = t; a->max_events = max_events; a->max_expired = max_expired;
+    rg::AsmParams &p = a->sc;
+    const size_t G = t->G, words = (G + 63) / 64, events = (size_t)max_events + max_expired, eb = events ? (events + 255) / 256 : 1;
+    p.groups = t->G; p.words = (uint32_t)words;
+    p.seg_cap = (uint32_t)events;
+    p.rows_cap = (uint32_t)(G < events ? G : events);                  // a listed row has an event: there are never more rows than events, or than groups
+    p.big_cap = (uint32_t)(events / (rg::ASM_SMALL + 1) + 1);          // ... and a row queued for asm_big_rows_kernel has more than ASM_SMALL of them
+    struct { void **ptr; size_t bytes; bool zero; } cols[] = {
+        {(void **)&p.cnt, G * sizeof(uint32_t), true}, {(void **)&p.bitmap, words * sizeof(unsigned long long), true}, {(void **)&p.rowof, G * sizeof(uint32_t), true},
+        {(void **)&p.wordoff, (words + 1) * sizeof(uint32_t), false}, {(void **)&p.rowcnt, ((size_t)p.rows_cap + 1) * sizeof(uint32_t), false},
+        {(void **)&p.segoff, ((size_t)p.rows_cap + 1) * sizeof(uint32_t), false}, {(void **)&p.seg, (events + 1) * sizeof(uint32_t), false},
+        {(void **)&p.flag, events + 1, false}, {(void **)&p.dcounts, (eb * 4 + 1) * sizeof(uint32_t), false}, {(void **)&p.big, (size_t)p.big_cap * sizeof(uint32_t), false},
+        {(void **)&p.scalars, rg::ASM_SCALARS * sizeof(uint32_t), true}};
+    for (auto &c : cols) {
+        hipError_t e = hipMalloc(c.ptr, c.bytes);
+        if (e == hipSuccess && c.zero) e = hipMemsetAsync(*c.ptr, 0, c.bytes, t->stream);
+        if (e != hipSuccess) {
+            assembler_release(a);
+            delete a;
+            return fail(t, -2, "rg_assembler_create: %zu bytes of scratch: %s", c.bytes, hipGetErrorString(e));
+        }
+    }
+    if (hipStreamSynchronize(t->stream) != hipSuccess) { assembler_release(a); delete a; return fail(t, -2, "rg_assembler_create: hipStreamSynchronize failed"); }
+    t->assemblers.push_back(a);
+    *out = a;
+    return 0;
+}
+
+// device_visible() under the caller's name: the device's address of `p`, or a refusal
+static int asm_visible(rg_table *t, const void *p, const char *what, void **out)
+{
+    *out = nullptr;
+    if (!p) return 0;
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type == hipMemoryTypeUnregistered) {
+        (void)hipGetLastError();
+        return fail(t, -1, "rg_assemble32: %s is neither device memory (rg_dev_alloc) nor page-locked host memory (rg_host_alloc)", what);
+    }
+    if (at.type == hipMemoryTypeHost) {
+        if (hipHostGetDevicePointer(out, const_cast<void *>(p), 0) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(t, -1, "rg_assemble32: %s is host memory the device cannot address", what);
+        }
+        return 0;
+    }
+    *out = const_cast<void *>(p);
+    return 0;
+}
+
+int rg_assemble32(rg_assembler_t *a, const rg_arrivals_t *in, const rg_assembled_t *out, int memspace)
+{
+    if (!a || !a->t) return -1;
+    rg_table *t = a->t;
+    const char *who = "rg_assemble32";
+    if (!in || !out) return fail(t, -1, "%s: NULL arrivals or batch", who);
+    if (!in->count || (in->capacity && (!in->gid || !in->head || !in->abcd))) return fail(t, -1, "%s: count, gid, head and abcd of the arrival log are required", who);
+    if (!out->gid || !out->count || !out->rounds || !out->head || !out->abcd || !out->origin || !out->stats || (out->deferred_capacity && !out->deferred))
+        return fail(t, -1, "%s: gid, count, rounds, head, abcd, origin and stats of the batch are required (and deferred, unless deferred_capacity is 0)", who);
+    if (out->capacity == 0 || out->capacity > t->G) return fail(t, -1, "%s: capacity %u outside 1 .. %u groups", who, out->capacity, t->G);
+    if (out->max_rounds < 1 || out->max_rounds > 64) return fail(t, -1, "%s: max_rounds %u outside 1 .. 64", who, out->max_rounds);
+    if (in->capacity > a->max_events) return fail(t, -1, "%s: an arrival log of %u events, the assembler was created for %u", who, in->capacity, a->max_events);
+    const int sources = (in->expired_gid != nullptr) + (in->expired_epoch != nullptr) + (in->expired_count != nullptr);
+    if (sources != 0 && sources != 3) return fail(t, -1, "%s: the expired source comes as all three columns or none", who);
+    const bool expired = sources == 3;
+    if (expired && in->expired_capacity > a->max_expired)
+        return fail(t, -1, "%s: an expired source of %u entries, the assembler was created for %u", who, in->expired_capacity, a->max_expired);
+    if (memspace != RG_MEM_DEVICE && memspace != RG_MEM_HOST) return fail(t, -1, "%s: unknown memspace %d", who, memspace);
+    const uint32_t C = out->capacity, D = out->max_rounds, ex_cap = expired ? in->expired_capacity : 0u;
+    const size_t cells = (size_t)C * D;
+    rg::AsmParams p = a->sc;
+    p.in_cap = in->capacity; p.ex_cap = ex_cap; p.C = C; p.D = D; p.deferred_cap = out->deferred_capacity;
+    if (memspace == RG_MEM_DEVICE) {
+        void *v[16] = {};
+        const struct { const void *ptr; const char *what; } cols[] = {
+            {in->count, "count"}, {in->gid, "gid"}, {in->head, "head"}, {in->abcd, "abcd"}, {in->expired_gid, "expired_gid"}, {in->expired_epoch, "expired_epoch"},
+            {in->expired_count, "expired_count"}, {out->gid, "the batch's gid"}, {out->count, "the batch's count"}, {out->rounds, "rounds"}, {out->head, "the batch's head"},
+            {out->abcd, "the batch's abcd"}, {out->origin, "origin"}, {out->deferred, "deferred"}, {out->stats, "stats"}};
+        int k = 0;
+        for (const auto &c : cols) if (int rc = asm_visible(t, c.ptr, c.what, &v[k++])) return rc;
+        p.in_count = (const uint32_t *)v[0]; p.in_gid = (const uint32_t *)v[1]; p.in_head = (const rg::U32x2 *)v[2]; p.in_abcd = (const rg::I32x4 *)v[3];
+        p.ex_gid = (const uint32_t *)v[4]; p.ex_epoch = (const uint32_t *)v[5]; p.ex_count = (const uint32_t *)v[6];
+        p.gid = (uint32_t *)v[7]; p.count = (uint32_t *)v[8]; p.rounds = (uint32_t *)v[9]; p.head = (rg::U32x2 *)v[10]; p.abcd = (rg::I32x4 *)v[11];
+        p.origin = (uint32_t *)v[12]; p.deferred = (uint32_t *)v[13]; p.stats = (uint32_t *)v[14];
+        if (bind(t)) return -2;
+        HIP_TRY(t, rg::launch_assemble(p, t->stream));
+        return 0;
+    }
+    if (bind(t)) return -2;
+    hipStream_t s = t->stream;
+    // host memory: stage the sources in (as much of them as this run reads), run, bring back what the run wrote — rows 0 .. n - 1 of rounds 0 .. R - 1 — and nothing else
+    const uint32_t m = *in->count < in->capacity ? *in->count : in->capacity;
+    const uint32_t e = !expired || *in->expired_count == 0xFFFFFFFFu ? 0u : (*in->expired_count < ex_cap ? *in->expired_count : ex_cap);
+    if (reserve(t, a->in_words, 2 * sizeof(uint32_t)) || reserve(t, a->in_gid, (size_t)m * sizeof(uint32_t)) || reserve(t, a->in_head, (size_t)m * sizeof(rg_ev_head_t)) ||
+        reserve(t, a->in_abcd, (size_t)m * sizeof(rg_ev_quad32_t)) || reserve(t, a->ex_gid, (size_t)e * sizeof(uint32_t)) || reserve(t, a->ex_epoch, (size_t)e * sizeof(uint32_t)) ||
+        reserve(t, a->out_gid, (size_t)C * sizeof(uint32_t)) || reserve(t, a->out_words, 6 * sizeof(uint32_t)) || reserve(t, a->out_head, cells * sizeof(rg_ev_head_t)) ||
+        reserve(t, a->out_abcd, cells * sizeof(rg_ev_quad32_t)) || reserve(t, a->out_origin, cells * sizeof(uint32_t)) ||
+        reserve(t, a->out_deferred, (size_t)out->deferred_capacity * sizeof(uint32_t)))
+        return -2;
+    const uint32_t words_in[2] = {*in->count, expired ? *in->expired_count : 0u};
+    HIP_TRY(t, hipMemcpyAsync(a->in_words.ptr, words_in, sizeof words_in, hipMemcpyHostToDevice, s));
+    if (m) {
+        HIP_TRY(t, hipMemcpyAsync(a->in_gid.ptr, in->gid, (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(t, hipMemcpyAsync(a->in_head.ptr, in->head, (size_t)m * sizeof(rg_ev_head_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(t, hipMemcpyAsync(a->in_abcd.ptr, in->abcd, (size_t)m * sizeof(rg_ev_quad32_t), hipMemcpyHostToDevice, s));
+    }
+    if (e) {
+        HIP_TRY(t, hipMemcpyAsync(a->ex_gid.ptr, in->expired_gid, (size_t)e * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(t, hipMemcpyAsync(a->ex_epoch.ptr, in->expired_epoch, (size_t)e * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    }
+    uint32_t *ow = (uint32_t *)a->out_words.ptr;                       // {n, R, stats[4]}
+    p.in_count = (const uint32_t *)a->in_words.ptr; p.in_gid = (const uint32_t *)a->in_gid.ptr;
+    p.in_head = (const rg::U32x2 *)a->in_head.ptr; p.in_abcd = (const rg::I32x4 *)a->in_abcd.ptr;
+    p.ex_gid = (const uint32_t *)a->ex_gid.ptr; p.ex_epoch = (const uint32_t *)a->ex_epoch.ptr; p.ex_count = expired ? (const uint32_t *)a->in_words.ptr + 1 : nullptr;
+    p.gid = (uint32_t *)a->out_gid.ptr; p.count = ow; p.rounds = ow + 1; p.stats = ow + 2;
+    p.head = (rg::U32x2 *)a->out_head.ptr; p.abcd = (rg::I32x4 *)a->out_abcd.ptr; p.origin = (uint32_t *)a->out_origin.ptr; p.deferred = (uint32_t *)a->out_deferred.ptr;
+    HIP_TRY(t, rg::launch_assemble(p, s));
+    uint32_t back[6] = {};
+    HIP_TRY(t, hipMemcpyAsync(back, ow, sizeof back, hipMemcpyDeviceToHost, s));
+    HIP_TRY(t, hipStreamSynchronize(s));
+    const uint32_t n = back[0], R = back[1];
+    *out->count = n; *out->rounds = R;
+    memcpy(out->stats, back + 2, 4 * sizeof(uint32_t));
+    if (n) {
+        HIP_TRY(t, hipMemcpyAsync(out->gid, a->out_gid.ptr, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        for (uint32_t r = 0; r < R; r++) {
+            const size_t at = (size_t)r * C;
+            HIP_TRY(t, hipMemcpyAsync(out->head + at, (rg_ev_head_t *)a->out_head.ptr + at, (size_t)n * sizeof(rg_ev_head_t), hipMemcpyDeviceToHost, s));
+            HIP_TRY(t, hipMemcpyAsync(out->abcd + at, (rg_ev_quad32_t *)a->out_abcd.ptr + at, (size_t)n * sizeof(rg_ev_quad32_t), hipMemcpyDeviceToHost, s));
+            HIP_TRY(t, hipMemcpyAsync(out->origin + at, (uint32_t *)a->out_origin.ptr + at, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        }
+    }
+    const uint32_t kept = back[3] < out->deferred_capacity ? back[3] : out->deferred_capacity;
+    if (kept) HIP_TRY(t, hipMemcpyAsync(out->deferred, a->out_deferred.ptr, (size_t)kept * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(t, hipStreamSynchronize(s));
     return 0;
 }
 

@@ -899,3 +899,9 @@ hipError_t launch_copy(const void *src, void *dst, size_t bytes, hipStream_t s)
 #endif
 
 }  // namespace rg
+
+// ---- arrival-ordered events into sparse-round batches (rg_assemble32): its kernels use timers_scan_kernel above ---------------------------------------------
+#ifdef RG_TU_MAIN
+#define RG_ASSEMBLE_KERNELS 1
+#endif
+#include "rg_assemble.hpp"

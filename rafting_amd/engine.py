@@ -31,7 +31,7 @@ def exported_symbols():
     """Every entry point include/raftgpu.h declares."""
     return [
         "rg_abi_version", "rg_table_create", "rg_table_destroy", "rg_last_error", "rg_table_groups",
-        "rg_table_cluster", "rg_table_option", "rg_load_state", "rg_read_state", "rg_submit", "rg_submit32", "rg_submit32c", "rg_submit32c_sparse", "rg_submit32c_sparse_rounds", "rg_outcome32_unpack", "rg_outcome32_unpack_rel", "rg_index_base_set", "rg_index_base_get", "rg_index_base_advance", "rg_index_base_advance32", "rg_batch32_pack_rel", "rg_batch32_pack", "rg_submit_async", "rg_submit_async_packed", "rg_submit_wait", "rg_tick_create", "rg_tick_launch", "rg_tick_wait", "rg_tick_destroy", "rg_tick2_create", "rg_tick2_create_sparse", "rg_tick2_create_sparse_rounds", "rg_tick2_launch", "rg_tick2_wait", "rg_tick2_destroy", "rg_timers_update32", "rg_health_update32", "rg_sync", "rg_step_kernel", "rg_host_alloc", "rg_host_free", "rg_dev_alloc",
+        "rg_table_cluster", "rg_table_option", "rg_load_state", "rg_read_state", "rg_submit", "rg_submit32", "rg_submit32c", "rg_submit32c_sparse", "rg_submit32c_sparse_rounds", "rg_outcome32_unpack", "rg_outcome32_unpack_rel", "rg_index_base_set", "rg_index_base_get", "rg_index_base_advance", "rg_index_base_advance32", "rg_batch32_pack_rel", "rg_batch32_pack", "rg_submit_async", "rg_submit_async_packed", "rg_submit_wait", "rg_tick_create", "rg_tick_launch", "rg_tick_wait", "rg_tick_destroy", "rg_tick2_create", "rg_tick2_create_sparse", "rg_tick2_create_sparse_rounds", "rg_tick2_launch", "rg_tick2_wait", "rg_tick2_destroy", "rg_assembler_create", "rg_assemble32", "rg_assembler_destroy", "rg_timers_update32", "rg_health_update32", "rg_sync", "rg_step_kernel", "rg_host_alloc", "rg_host_free", "rg_dev_alloc",
         "rg_dev_free", "rg_copy_to_device", "rg_copy_to_host", "rg_stream", "rg_replicate", "rg_timers_configure", "rg_timers_update",
         "rg_timers_expired", "rg_timers_expired_epochs", "rg_timers_arm", "rg_timers_read", "rg_health_update", "rg_health_failure", "rg_ready", "rg_health_read",
         "rg_timing_enable",
@@ -131,6 +131,9 @@ def lib():
         L.rg_tick2_launch.argtypes = [vp]
         L.rg_tick2_wait.argtypes = [vp]
         L.rg_tick2_destroy.argtypes = [vp]
+        L.rg_assembler_create.argtypes = [vp, u32, u32, C.POINTER(vp)]
+        L.rg_assemble32.argtypes = [vp, C.POINTER(abi.CArrivals), C.POINTER(abi.CAssembled), i32]
+        L.rg_assembler_destroy.argtypes = [vp]
         L.rg_timers_update32.argtypes = [vp, u32, vp, vp, vp, i32]
         L.rg_health_update32.argtypes = [vp, u32, vp, vp, vp, i32]
         L.rg_replicate.argtypes = [vp, u32, vp, vp, vp, vp, vp, i32]
@@ -522,6 +525,66 @@ class Tick2:
         for b in self._devs:
             b.free()
         self._pins, self._devs = [], []
+
+
+class Assembler:
+    """rg_assembler_create / rg_assemble32: arrival-ordered events (and the tickets a tick listed) into the [round][row] columns of a sparse-rounds batch, on the
+    device. assemble() is the RG_MEM_HOST form on numpy arrays; run_device() queues one RG_MEM_DEVICE run on the table's stream from two structs whose pointers are
+    device-visible (abi.CArrivals / abi.CAssembled — for instance over the columns of a Tick2 recorded with sparse_rounds=True: for_tick())."""
+
+    def __init__(self, table, max_events, max_expired=0):
+        self.table, self.max_events, self.max_expired = table, int(max_events), int(max_expired)
+        h = C.c_void_p()
+        table._check(lib().rg_assembler_create(table._h, self.max_events, self.max_expired, C.byref(h)))
+        self._h = h
+
+    def run_device(self, arrivals, assembled):
+        self.table._check(lib().rg_assemble32(self._h, C.byref(arrivals), C.byref(assembled), abi.MEM_DEVICE))
+
+    def assemble(self, gid, head, abcd, capacity, max_rounds, expired=None, deferred_capacity=None, fill=0xAB, count=None):
+        """one synchronous run on host arrays -> SimpleNamespace(n, R, gid[n], head / abcd / origin as [D][C] images that held `fill` bytes before the run,
+        deferred (what the list holds of the stats[1] ids), stats[4]). expired: (gids, epochs, count) or None; count: *count of the log (default: its length)."""
+        import types
+        gid = np.ascontiguousarray(gid, dtype=np.uint32)
+        head, abcd = np.ascontiguousarray(head, dtype=abi.HEAD_DT), np.ascontiguousarray(abcd, dtype=abi.QUAD32_DT)
+        m, Cc, D = len(gid), int(capacity), int(max_rounds)
+        dcap = m + (len(expired[0]) if expired is not None else 0) if deferred_capacity is None else int(deferred_capacity)
+        cnt = np.array([m if count is None else count], np.uint32)
+        a = abi.CArrivals()
+        a.count, a.capacity, a.gid, a.head, a.abcd = cnt.ctypes.data, m, gid.ctypes.data, head.ctypes.data, abcd.ctypes.data
+        keep = [gid, head, abcd, cnt]
+        if expired is not None:
+            eg, ee = np.ascontiguousarray(expired[0], dtype=np.uint32), np.ascontiguousarray(expired[1], dtype=np.uint32)
+            ec = np.array([expired[2]], np.uint32)
+            a.expired_gid, a.expired_epoch, a.expired_count, a.expired_capacity = eg.ctypes.data, ee.ctypes.data, ec.ctypes.data, len(eg)
+            keep += [eg, ee, ec]
+        cells = max(Cc * D, 1)
+        out = types.SimpleNamespace(gid=np.full(max(Cc, 1), fill * 0x01010101, np.uint32), count=np.zeros(1, np.uint32), rounds=np.zeros(1, np.uint32),
+                                    head=np.zeros(cells, abi.HEAD_DT), abcd=np.zeros(cells, abi.QUAD32_DT), origin=np.zeros(cells, np.uint32),
+                                    deferred=np.full(max(dcap, 1), fill * 0x01010101, np.uint32), stats=np.zeros(4, np.uint32))
+        for col in (out.head, out.abcd, out.origin):
+            col.view(np.uint8)[:] = fill
+        b = abi.CAssembled()
+        b.capacity, b.max_rounds, b.gid, b.count, b.rounds = Cc, D, out.gid.ctypes.data, out.count.ctypes.data, out.rounds.ctypes.data
+        b.head, b.abcd, b.origin, b.deferred, b.deferred_capacity, b.stats = (out.head.ctypes.data, out.abcd.ctypes.data, out.origin.ctypes.data,
+                                                                              out.deferred.ctypes.data, dcap, out.stats.ctypes.data)
+        self.table._check(lib().rg_assemble32(self._h, C.byref(a), C.byref(b), abi.MEM_HOST))
+        out.n, out.R, out.deferred_capacity = int(out.count[0]), int(out.rounds[0]), dcap
+        return out
+
+    def for_tick(self, tick, origin, deferred, deferred_capacity, stats):
+        """-> the abi.CAssembled over the gid / count / depth / head / abcd columns of a Tick2 recorded with sparse_rounds=True (origin [rounds * capacity], deferred and
+        stats [4]: device-visible addresses)"""
+        assert tick.deep and not tick.fixed_depth
+        b = abi.CAssembled()
+        b.capacity, b.max_rounds, b.gid, b.count, b.rounds = tick.G, tick.rounds, tick.rows.gid, tick.rows.count, tick.rows.rounds
+        b.head, b.abcd, b.origin, b.deferred, b.deferred_capacity, b.stats = tick.io.head, tick.io.abcd, origin, deferred, deferred_capacity, stats
+        return b
+
+    def close(self):
+        if self._h:
+            lib().rg_assembler_destroy(self._h)
+            self._h = None
 
 
 class DeviceBuffer:
