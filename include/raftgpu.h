@@ -64,7 +64,9 @@ extern "C" {
                                      6: automatic index bases: RG_OPT_AUTO_INDEX_BASE, rg_index_base_advance / rg_index_base_advance32
                                         (still 6, new symbols only — nothing that existed changed: rg_submit32c_sparse, rg_tick2_rows_t, rg_tick2_create_sparse;
                                          then rg_submit32c_sparse_rounds, rg_tick2_rounds_t, rg_tick2_create_sparse_rounds: a list of groups with R rounds;
-                                         then RG_OPT_COMPACT_ANY_CLUSTER: a new value of the option enum, no new symbol, no struct change) */
+                                         then RG_OPT_COMPACT_ANY_CLUSTER: a new value of the option enum, no new symbol, no struct change;
+                                         then RG_OPT_DEVICE_IN_FLIGHT: a new option value, rg_in_flight_read / rg_in_flight_set, RG_HEALTH_NO_REQUEST, and — with the option on
+                                         only — a meaning for rg_send_head_t.reserved, which stays 0 without it) */
 #define RG_MIN_CLUSTER      2     /* P: cluster size incl. self (RaftCluster.size()) */
 #define RG_MAX_CLUSTER      15    /* (ABI 5; the slot field of a row header is 4 bits. Leadership.majorIndices sorts any number of followers, member/Leadership.java:116-130.)
                                      Every cluster size has the wide-row entry points (rg_submit, rg_submit_async). The compact formats (rg_submit32*, rg_submit_async_packed)
@@ -283,7 +285,7 @@ enum { RG_OPT_REQUIRE_FENCED_TIMEOUTS = 1,
        RG_OPT_AUTO_INDEX_BASE = 2,          /* (ABI 6) value = the window W of the automatic index bases: 0 = off (default), 1 <= W < 2^30 = on, anything else -1.
                                                See "THE INDEX BASE OF THE COMPACT FORMATS" below. Switching it on or off bumps what a recorded tick has baked in:
                                                rg_tick_launch / rg_tick2_launch of an earlier recording then refuse (-1). Recommended window: 2^28. */
-       RG_OPT_COMPACT_ANY_CLUSTER = 3 };    /* value 0 (default): the compact formats and the ticks refuse a table of more than RG_MAX_COMPACT_CLUSTER nodes (-1, "wide rows").
+       RG_OPT_COMPACT_ANY_CLUSTER = 3,      /* value 0 (default): the compact formats and the ticks refuse a table of more than RG_MAX_COMPACT_CLUSTER nodes (-1, "wide rows").
                                                value 1: they take the table's cluster size, whatever it is (2 .. RG_MAX_CLUSTER): rg_submit32, rg_submit32c, rg_submit32c_sparse,
                                                rg_submit32c_sparse_rounds, rg_submit_async_packed, rg_tick_create, rg_tick2_create, rg_tick2_create_sparse,
                                                rg_tick2_create_sparse_rounds — same rows, same outcomes, bit-identical to the wide-row entry points. Any other value: -1.
@@ -294,6 +296,14 @@ enum { RG_OPT_REQUIRE_FENCED_TIMEOUTS = 1,
                                                wavefronts per SIMD at 8 followers, two at 14. Its rate against the wide-row kernels has NOT been measured yet (DESIGN.md
                                                section 6, "Compact rows above 7 nodes", names the measurement): until it is, the option buys the formats and the ticks,
                                                not a known speed. The C++ ingress / flusher and the Java row packer do not set the option. */
+       RG_OPT_DEVICE_IN_FLIGHT = 4 };       /* value 0 (default): nothing changes anywhere — the send step of a tick reads the caller's heartbeat[] / in_flight[] columns.
+                                               value 1: the table keeps State.requestInFlight (member/Leadership.java:31) itself, one uint16_t per (follower, group), laid out
+                                               like the health columns, zero when the option is switched on (switching it off drops the counts), and the send step of a recorded
+                                               tick needs no host column: see "THE SEND STEP WITH DEVICE-RESIDENT IN-FLIGHT COUNTS" at rg_tick2_io_t. rg_load_state zeroes the
+                                               counts of the groups it loads, as it resets their health; rg_health_failure takes the failed requests off; rg_in_flight_read /
+                                               rg_in_flight_set read and write them. rg_replicate is unchanged: it keeps its explicit columns and never touches the counts.
+                                               Any other value: -1. Like every option it is part of a recording: rg_tick2_launch refuses a tick recorded before it changed.
+                                               The C++ ingress / flusher, the JNI shim and the Java packer do not set it. */
 int         rg_table_option(rg_table_t *t, int option, int value);
 uint32_t    rg_table_groups(const rg_table_t *t);
 uint32_t    rg_table_cluster(const rg_table_t *t);
@@ -515,8 +525,12 @@ typedef struct {                 /* one per row */
     int64_t  epoch_term;
     uint32_t role_epoch;         /* tag for the response rows                      */
     uint32_t is_leader;          /* 0: every send of this row is RG_SEND_NONE      */
-    uint64_t reserved;           /* 0; pads the row to three 16-byte words so a wavefront stores whole 1 KiB lines */
+    uint64_t reserved;           /* pads the row to three 16-byte words so a wavefront stores whole 1 KiB lines. 0 — except in the send step of a tick on a table
+                                    with RG_OPT_DEVICE_IN_FLIGHT, where it says what the tick derived for the row: RG_SENT_TRIGGERED | RG_SENT_HEARTBEAT */
 } rg_send_head_t;                /* 48 B */
+
+#define RG_SENT_TRIGGERED  1u    /* rg_send_head_t.reserved, RG_OPT_DEVICE_IN_FLIGHT: a handler of the row's rounds sent (acceptCommand or onTimeout); clear: every send is RG_SEND_NONE */
+#define RG_SENT_HEARTBEAT  2u    /* ... and it was onTimeout alone: replicateLog(true), fetch limit 25, in-flight limit 2 */
 
 typedef struct {                 /* one per (row, follower j); j = slot<self ? slot : slot-1 */
     int64_t  prev_index;
@@ -577,17 +591,27 @@ int rg_timers_read(rg_table_t *t, uint32_t first, uint32_t count, int64_t *deadl
  *                      became Leader gets fresh State objects (all zero).
  *   rg_health_failure  statFailure(now, unreachable, reject) for RPCs that ended in an error / timeout on the host
  *                      (flags bit0 = unreachable, bit1 = reject; reject also bumps recentRejection of the table).
+ *                      With RG_OPT_DEVICE_IN_FLIGHT it is also the callback's requestInFlight-- (member/Leader.java:176,221, then statFailure): the count
+ *                      of every (gid, slot) given goes down by one per entry, clamped at 0, whatever the group's role — EXCEPT for an entry with bit2,
+ *                      RG_HEALTH_NO_REQUEST: the "service is not available" call of Leader.java:242, where nothing was sent; its statistics are as always
+ *                      and no count moves. Entries may repeat a (gid, slot) pair; each takes one off. Without the option bit2 is ignored.
  *   rg_ready           Leader.isReady per group: 1 when self + healthy followers exceed half the followers, else 0
  *                      (0 for non-leaders and for leaders that have not prepared replication). */
 int rg_health_update(rg_table_t *t, uint32_t rounds, uint32_t count, const uint32_t *gid, const rg_ev_head_t *head,
                      const rg_reply_t *reply, const int64_t *now, int memspace);
 /* rg_health_update from compact outcome rows (ABI 5; dense): head = the batch's event heads, row = its rg_out32_t column */
 int rg_health_update32(rg_table_t *t, uint32_t rounds, const rg_ev_head_t *head, const rg_out32_t *row, const int64_t *now, int memspace);
+#define RG_HEALTH_NO_REQUEST 4u
 int rg_health_failure(rg_table_t *t, uint32_t n, const uint32_t *gid, const uint8_t *slot, const uint8_t *flags, int64_t now);
 int rg_ready(rg_table_t *t, int64_t now, int32_t critical_point, int64_t cool_down_ms, uint8_t *ready, int memspace);
 /* request_success / request_failure / recent_failure: [count * (cluster-1)], index g*(P-1)+j like rg_group_state_t peers */
 int rg_health_read(rg_table_t *t, uint32_t first, uint32_t count, int64_t *request_success, int64_t *request_failure,
                    int32_t *recent_failure);
+/* State.requestInFlight of groups [first, first + count) as a table with RG_OPT_DEVICE_IN_FLIGHT keeps it: in_flight is [count * (cluster-1)], index g*(P-1)+j like
+ * rg_health_read. rg_in_flight_set overwrites the counts (a restart that knows what is outstanding; tests). Both wait for the table's stream; both answer -1 with a
+ * message while the option is off. */
+int rg_in_flight_read(rg_table_t *t, uint32_t first, uint32_t count, uint16_t *in_flight);
+int rg_in_flight_set(rg_table_t *t, uint32_t first, uint32_t count, const uint16_t *in_flight);
 
 /* ---- THE DEVICE-RESIDENT TICK (ABI 5) --------------------------------------------------------------------------------------------------
  * "closes the loop leader-step -> follower-step on device". One tick of a node, recorded ONCE as a HIP graph on the table's stream
@@ -603,7 +627,29 @@ int rg_health_read(rg_table_t *t, uint32_t first, uint32_t count, int64_t *reque
  * it lies, so the caller decides per column what stays in HBM (the rows of a resident replay, the send table a gateway kernel consumes) and what crosses
  * the link (the expired list, a few counters). The per-round clocks are READ from `now` when the graph runs: refill rows and clocks, launch, wait.
  * Decisions, deadlines, statistics and send rows are those of the separate calls (tests/test_gpu_parity.py::test_the_device_resident_tick_matches_the_oracle).
- * The table's options and index bases at creation are part of the recording: rg_tick2_launch refuses (-1) when they have changed since.            */
+ * The table's options and index bases at creation are part of the recording: rg_tick2_launch refuses (-1) when they have changed since.
+ *
+ * THE SEND STEP WITH DEVICE-RESIDENT IN-FLIGHT COUNTS (RG_OPT_DEVICE_IN_FLIGHT = 1). heartbeat[] and in_flight[] are per row, so a host that fills them must know which
+ * group sits in which row — which a tick fed by rg_assemble32 does not. With the option on, all three of rg_tick2_create, rg_tick2_create_sparse and
+ * rg_tick2_create_sparse_rounds REFUSE a non-NULL io->heartbeat or io->in_flight (-1, a message that names the option, nothing recorded), and a tick that has a send step
+ * (send_head != NULL) derives both from its own rows. For every row it decides, over that row's rounds 0 .. R - 1 in order:
+ *   - a row with RG_F_ROLE_CHANGED forgets the trigger collected so far; if the role after it is Leader it zeroes the group's P - 1 counts (fresh State objects: what
+ *     the fold does for the health statistics);
+ *   - an RG_EV_AE_ACK / RG_EV_IS_ACK row takes one off the count of its follower, clamped at 0, unless its status is RG_DROPPED_STALE_ROLE or RG_BAD_EVENT, it carries
+ *     RG_F_ROLE_CHANGED, or its slot is not a follower's. The callback decrements before it looks at the result (member/Leader.java:176,221): reached, success and a
+ *     mismatch status do not matter; a stale ack belongs to State objects that no longer exist;
+ *   - the trigger: `command` = an RG_EV_CLIENT_APPEND row with status RG_OK and RG_F_LOG_APPEND (acceptCommand); `heartbeat` = a row whose RG_F_EMIT is
+ *     RG_EMIT_HEARTBEAT (a Leader's onTimeout). A row with any command sends as acceptCommand (fetch limit 50, in-flight limit 20) whatever else it holds; one with
+ *     heartbeats only as onTimeout (25, 2); one with neither does not send.
+ * THE SENDS OF A ROW'S ROUNDS COLLAPSE INTO ONE PLAN, taken after round R - 1 — as they always have in a tick: the reference would have sent once per handler.
+ *   - a triggered row: send_head[row] and send[j][row] are exactly what rg_replicate(t, 1, &gid, &hb, counts, ..) gives at that point, hb from the trigger, counts =
+ *     the group's counts after the decrements above; every follower whose kind comes out RG_SEND_APPEND, RG_SEND_SNAPSHOT or RG_SEND_NEED_HOST gets +1 (saturating at
+ *     65 535), RG_SEND_GATED and RG_SEND_NONE nothing;
+ *   - a row without a trigger (say, one whose only event was an ack): the head's scalar fields and is_leader are the group's, every send is {0, 0, 0, 0, RG_SEND_NONE},
+ *     Leader.prepareReplication does NOT run, no count goes up. (Without the option rg_replicate's answer is written for every listed leader row.)
+ *   - send_head.reserved carries RG_SENT_TRIGGERED and RG_SENT_HEARTBEAT (0 with the option off).
+ * Rows >= n and rounds >= R stay untouched, as always; the counts of groups outside a sparse tick's list are not touched. A tick without a send step moves no count.
+ * The dense tick's step-by-step recording (RG_TICK_NODES=4, an experiment knob) is recorded as RG_TICK_NODES=2 with the option on.            */
 typedef struct {
     /* in */
     uint32_t              rounds;           /* 1 .. 64; count is the table's group count (dense). rg_tick2_create_sparse: 1, and every G below reads `capacity`; rg_tick2_create_sparse_rounds: the greatest depth */
@@ -612,8 +658,8 @@ typedef struct {
     const int32_t        *entry_terms;      /* [entry_capacity] or NULL */
     uint64_t              entry_capacity;
     const int64_t        *now;              /* [rounds] clock of every round; now[rounds - 1] is "now" for expiry and readiness */
-    const uint8_t        *heartbeat;        /* [G] rg_replicate's per-row flag, or NULL (all 0) */
-    const uint16_t       *in_flight;        /* [(P - 1) * G] or NULL */
+    const uint8_t        *heartbeat;        /* [G] rg_replicate's per-row flag, or NULL (all 0). Must be NULL on a table with RG_OPT_DEVICE_IN_FLIGHT */
+    const uint16_t       *in_flight;        /* [(P - 1) * G] or NULL. Must be NULL on a table with RG_OPT_DEVICE_IN_FLIGHT */
     int32_t               critical_point;   /* rg_ready's availableCriticalPoint / recoveryCoolDownMills */
     int64_t               cool_down_ms;
     /* out */
@@ -644,7 +690,8 @@ int rg_tick2_create(rg_table_t *t, const rg_tick2_io_t *io, rg_tick2_t **tick);
  * the whole column); (5) the tickets that fired by now[0] in the WHOLE TABLE, ascending, with their role epochs, marked fired — as in the dense tick. n = 0 is a
  * legal tick: only (5) happens. The handle is an ordinary rg_tick2_t: rg_tick2_launch / _wait / _destroy, the refusal after a change of options or index bases and
  * the behaviour of a tick that outlives its table are those of the dense tick. With the list gid[i] = i, n = capacity = groups, every column equals the dense
- * tick's. Which of the two to record is the caller's choice: it knows its fill. */
+ * tick's. Which of the two to record is the caller's choice: it knows its fill. With RG_OPT_DEVICE_IN_FLIGHT step (3) is the derived one described above: heartbeat and
+ * in_flight must be NULL, a listed leader sends only where a handler of its row sent, and the counts of the listed groups move. */
 typedef struct {
     const uint32_t *gid;       /* [capacity] group of row i; the first n entries strictly ascending, each below the table's group count */
     const uint32_t *count;     /* [1] rows of THIS tick, read when the graph runs; n = min(*count, capacity) */
@@ -666,7 +713,8 @@ int rg_tick2_create_sparse(rg_table_t *t, const rg_tick2_io_t *io, const rg_tick
  * io->rounds == 1 every column equals rg_tick2_create_sparse's. The handle is an ordinary rg_tick2_t: launch / wait / destroy, the refusal after a change of options or
  * index bases and a tick that outlives its table are all as above. Refused before anything is recorded, each with a message: a missing gid / count, a capacity of 0 or
  * above the group count, io->rounds outside 1 .. 64, a column or a `rounds` that is not device-visible, a cluster above RG_MAX_COMPACT_CLUSTER unless the table has
- * RG_OPT_COMPACT_ANY_CLUSTER. */
+ * RG_OPT_COMPACT_ANY_CLUSTER; io->heartbeat or io->in_flight on a table with RG_OPT_DEVICE_IN_FLIGHT. With that option step (3) is the derived one described at
+ * rg_tick2_io_t: the row's rounds 0 .. R - 1 are walked in order, one plan after round R - 1. */
 typedef struct {
     const uint32_t *gid;       /* [capacity] as rg_tick2_rows_t */
     const uint32_t *count;     /* [1] rows of THIS tick, n = min(*count, capacity), read when the graph runs */
@@ -712,7 +760,7 @@ int rg_tick2_destroy(rg_tick2_t *tick);
  * asynchronous on the table's stream, synchronises nothing and decides nothing on the host from device data — its grids are sized from the capacities and leave
  * early on the counts they read when they run (the counts and the entries below them stand still from the call until the run has executed; a reader may append BEYOND *count). So a run can be followed on the same stream by rg_tick2_launch of a recording made over the very same gid / count /
  * rounds / head / abcd buffers (rg_tick2_create_sparse_rounds with capacity C and io->rounds D), with the previous tick's expired_* columns as the second source: the
- * host knows neither n nor R. RG_MEM_HOST: host arrays, staged in and out, synchronous, after the pipeline has drained like every other entry point.
+ * host knows neither n nor R — and on a table with RG_OPT_DEVICE_IN_FLIGHT the send step of that tick needs no per-row column from it either. RG_MEM_HOST: host arrays, staged in and out, synchronous, after the pipeline has drained like every other entry point.
  * The assembler owns the scratch of its runs (about 8 bytes per group and 9 per event) and belongs to its table: destroy it before the table; one run at a time.
  * Refused (-1, with a message, before any launch): a missing column (deferred may be NULL with deferred_capacity 0), C = 0 or above the group count, D outside
  * 1 .. 64, an arrival or expired capacity above what the assembler was created for, an expired source given in part, an unknown memspace and, in RG_MEM_DEVICE, a

@@ -44,6 +44,9 @@ MEM_HOST, MEM_DEVICE = 0, 1
 OPT_REQUIRE_FENCED_TIMEOUTS = 1
 OPT_AUTO_INDEX_BASE = 2              # (ABI 6) window W of the automatic index bases, 0 = off; 2^28 recommended (include/raftgpu.h)
 OPT_COMPACT_ANY_CLUSTER = 3          # 1: the compact formats and the ticks take clusters above MAX_COMPACT_CLUSTER nodes too (include/raftgpu.h); 0 = off
+OPT_DEVICE_IN_FLIGHT = 4             # 1: the table keeps State.requestInFlight per (follower, group) and a tick's send step derives heartbeat / in_flight itself (include/raftgpu.h); 0 = off
+SENT_TRIGGERED, SENT_HEARTBEAT = 1, 2  # rg_send_head_t.reserved of a tick's send step on a table with OPT_DEVICE_IN_FLIGHT
+HEALTH_UNREACHABLE, HEALTH_REJECT, HEALTH_NO_REQUEST = 1, 2, 4      # rg_health_failure's flag bits
 NUM_COUNTERS = 8
 
 HEAD_DT = np.dtype([("hdr", "<u4"), ("aux", "<u4")])

@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "rg_device.hpp"
@@ -23,7 +24,7 @@ hipError_t launch_step(const StepParams &p, int followers, bool sparse, int shap
 hipError_t launch_copy(const void *src, void *dst, size_t bytes, hipStream_t s);
 hipError_t launch_replicate(const ReplicateParams &p, int followers, hipStream_t s);
 hipError_t launch_health_update(const HealthParams &p, hipStream_t s);
-hipError_t launch_health_failure(const HealthParams &p, uint32_t n, const uint32_t *gid, const uint8_t *slot, const uint8_t *flags, hipStream_t s);
+hipError_t launch_health_failure(const HealthParams &p, uint32_t n, const uint32_t *gid, const uint8_t *slot, const uint8_t *flags, const uint16_t *done, hipStream_t s);
 hipError_t launch_ready(const HealthParams &p, int64_t now, int32_t cp, int64_t cd, uint8_t *ready, hipStream_t s);
 hipError_t launch_timers_update(const TimerParams &p, hipStream_t s);
 hipError_t launch_tick_fold(const TickFoldParams &p, hipStream_t s);
@@ -92,6 +93,8 @@ struct rg_table {
     Staging st_tgid, st_hgid, st_hslot, st_hflag, st_ready;
     int64_t *health_ok = nullptr, *health_fail = nullptr;   // [F][G] N4b
     int32_t *health_recent = nullptr;
+    uint16_t *in_flight = nullptr;              // [F][G] State.requestInFlight; allocated while rg_table_option(RG_OPT_DEVICE_IN_FLIGHT) is 1, nullptr otherwise
+    Staging st_hdone;
     hipStream_t s_in = nullptr, s_out = nullptr; // copy-in / copy-out streams of the pipelined path
     PipeSlot pipe[RG_PIPELINE_DEPTH];
     uint64_t pipe_head = 0, pipe_tail = 0;       // batches submitted / waited for
@@ -186,6 +189,27 @@ int rg_table_option(rg_table_t *t, int option, int value)
         if (t->compact_any_cluster != value) t->config_gen += 1;        // (a tick recorded under one setting does not launch under the other)
         t->compact_any_cluster = value;
         return 0;
+    case RG_OPT_DEVICE_IN_FLIGHT: {
+        if (value != 0 && value != 1) return fail(t, -1, "rg_table_option: RG_OPT_DEVICE_IN_FLIGHT takes 0 or 1 (%d given)", value);
+        if ((t->in_flight != nullptr) == (value == 1)) return 0;
+        if (bind(t)) return -2;
+        HIP_TRY(t, hipStreamSynchronize(t->stream));
+        if (value == 1) {
+            const size_t bytes = (size_t)t->G * t->F * sizeof(uint16_t);
+            uint16_t *c = nullptr;
+            HIP_TRY(t, hipMalloc((void **)&c, bytes));
+            if (hipError_t e = hipMemsetAsync(c, 0, bytes, t->stream); e != hipSuccess || (e = hipStreamSynchronize(t->stream)) != hipSuccess) {
+                (void)hipFree(c);
+                return fail(t, -2, "rg_table_option: RG_OPT_DEVICE_IN_FLIGHT: %s", hipGetErrorString(e));
+            }
+            t->in_flight = c;
+        } else {
+            HIP_TRY(t, hipFree(t->in_flight));
+            t->in_flight = nullptr;
+        }
+        t->config_gen += 1;                                             // (a recorded tick has the column, or its absence, baked in)
+        return 0;
+    }
     default: return fail(t, -1, "rg_table_option: unknown option %d", option);
     }
 }
@@ -209,7 +233,7 @@ int rg_table_destroy(rg_table_t *t)
                     t->st_cd.ptr, t->st_hint.ptr, t->st_terms.ptr, t->st_reply.ptr, t->st_logfx.ptr,
                     t->st_persist.ptr, t->st_hb.ptr, t->st_fl.ptr, t->st_sh.ptr, t->st_ss.ptr, t->timer_deadline, t->timer_epoch, t->tick_masks, t->tick_ticket,
                     t->timer_counts, t->st_tgid.ptr, t->st_hgid.ptr, t->st_hslot.ptr, t->st_hflag.ptr, t->st_ready.ptr, t->health_ok,
-                    t->health_fail, t->health_recent, t->st_abcd32.ptr, t->st_terms32.ptr, t->st_out32.ptr, t->st_persist32.ptr};
+                    t->health_fail, t->health_recent, t->in_flight, t->st_hdone.ptr, t->st_abcd32.ptr, t->st_terms32.ptr, t->st_out32.ptr, t->st_persist32.ptr};
     for (void *c : cols) if (c) (void)hipFree(c);
     for (PipeSlot &sl : t->pipe) {
         if (sl.down) (void)hipEventSynchronize(sl.down);
@@ -402,6 +426,7 @@ int rg_load_state(rg_table_t *t, uint32_t first, uint32_t count, const rg_group_
         HIP_TRY(t, hipMemsetAsync(t->health_ok + j * G + first, 0, n * sizeof(int64_t), st));
         HIP_TRY(t, hipMemsetAsync(t->health_fail + j * G + first, 0, n * sizeof(int64_t), st));
         HIP_TRY(t, hipMemsetAsync(t->health_recent + j * G + first, 0, n * sizeof(int32_t), st));
+        if (t->in_flight) HIP_TRY(t, hipMemsetAsync(t->in_flight + j * G + first, 0, n * sizeof(uint16_t), st));   // ... with nothing in flight
     }
     HIP_TRY(t, hipStreamSynchronize(st));
     return 0;
@@ -892,6 +917,8 @@ static int tick2_create(rg_table_t *t, const rg_tick2_io_t *io, const rg_tick2_r
     if (io->entry_capacity && !io->entry_terms) return fail(t, -1, "%s: entry_capacity %llu without entry_terms", who, (unsigned long long)io->entry_capacity);
     if (io->expired_gid && (!io->expired_count || io->expired_capacity == 0)) return fail(t, -1, "%s: the expiry step needs expired_count and a capacity", who);
     if ((io->send_head == nullptr) != (io->send == nullptr)) return fail(t, -1, "%s: send_head and send come together", who);
+    if (t->in_flight && (io->heartbeat || io->in_flight))
+        return fail(t, -1, "%s: the table has RG_OPT_DEVICE_IN_FLIGHT: the send step derives heartbeat and in_flight from the tick's own rows, both columns must be NULL", who);
     if (rows) {
         if (io->rounds != 1 && !deep) return fail(t, -1, "%s: %u rounds (a list of groups carries exactly one round)", who, io->rounds);
         if (!rows->gid || !rows->count) return fail(t, -1, "%s: gid and count are required", who);
@@ -933,6 +960,9 @@ static int tick2_create(rg_table_t *t, const rg_tick2_io_t *io, const rg_tick2_r
     rp.now_mem = now_last;
     rg::ReplicateParams qp{};
     qp.t = t->dt; qp.count = R; qp.gid = (const uint32_t *)d_gid; qp.heartbeat = (const uint8_t *)d_hb; qp.in_flight = (const uint16_t *)d_fl; qp.head = (rg_send_head_t *)d_sh; qp.send = (rg_send_t *)d_ss;
+    if (t->in_flight) {                                      // RG_OPT_DEVICE_IN_FLIGHT: the send step reads the tick's own rows and the table's counts (rg_kernels.hip, replicate_wave)
+        qp.counts = t->in_flight; qp.ev_head = (const rg_ev_head_t *)d_head; qp.ev_out32 = (const rg::I32x4 *)d_row; qp.ev_stride = R; qp.self = t->self;
+    }
     hipStream_t s = t->stream;
     // What follows the decisions — what the batch did to the timers and to the followers' health, the list of the tickets that fired, the leaders' sends, the
     // readiness column — is one lane per group with same-group dependencies only, and a single-round tick is launch-bound (~14 us per graph node for ~10 us of
@@ -948,7 +978,8 @@ static int tick2_create(rg_table_t *t, const rg_tick2_io_t *io, const rg_tick2_r
     rg::TickTailParams tt{};
     tt.fp = fp; tt.qp = qp; tt.rp = rp; tt.critical_point = io->critical_point; tt.cool_down = io->cool_down_ms; tt.ready = (uint8_t *)d_ready;
     const char *nodes_env = getenv("RG_TICK_NODES");
-    const int nodes = (nodes_env && (nodes_env[0] == '2' || nodes_env[0] == '4')) ? nodes_env[0] - '0' : (sp.force_wide != 0 ? 2 : 1);
+    int nodes = (nodes_env && (nodes_env[0] == '2' || nodes_env[0] == '4')) ? nodes_env[0] - '0' : (sp.force_wide != 0 ? 2 : 1);
+    if (nodes == 4 && t->in_flight) nodes = 2;              // (the stand-alone replicate kernel has no rows to walk: include/raftgpu.h)
     hipError_t e = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
     if (rows) {
         // the sparse tick has ONE recording: the rows' workgroups (rg_kernels.hip, tick_sparse_kernel), then — it covers the whole table, whatever the list — the expiry
@@ -1771,6 +1802,7 @@ static rg::HealthParams health_params(rg_table *t)
     rg::HealthParams p{};
     p.ok = t->health_ok; p.fail = t->health_fail; p.recent = t->health_recent; p.t = t->dt;
     p.followers = t->F; p.self = t->self;
+    p.counts = t->in_flight;
     return p;
 }
 
@@ -1853,8 +1885,22 @@ int rg_health_failure(rg_table_t *t, uint32_t n, const uint32_t *gid, const uint
     HIP_TRY(t, hipMemcpyAsync(t->st_hflag.ptr, flags, n, hipMemcpyHostToDevice, s));
     rg::HealthParams p = health_params(t);
     p.now[0] = now;
+    std::vector<uint16_t> done;
+    if (t->in_flight) {
+        // requestInFlight-- per failed request (RG_HEALTH_NO_REQUEST: none was sent). Entries may repeat a (group, follower): their sum goes onto the first of
+        // them, so that one lane of the kernel owns a counter
+        done.assign(n, 0);
+        std::unordered_map<uint64_t, uint32_t> first_of;
+        for (uint32_t i = 0; i < n; i++) {
+            if (flags[i] & RG_HEALTH_NO_REQUEST) continue;
+            const uint32_t at = first_of.emplace(((uint64_t)gid[i] << 8) | slot[i], i).first->second;
+            if (done[at] != 0xFFFFu) done[at] += 1;
+        }
+        if (reserve(t, t->st_hdone, n * sizeof(uint16_t))) return -2;
+        HIP_TRY(t, hipMemcpyAsync(t->st_hdone.ptr, done.data(), n * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+    }
     HIP_TRY(t, rg::launch_health_failure(p, n, (const uint32_t *)t->st_hgid.ptr, (const uint8_t *)t->st_hslot.ptr,
-                                         (const uint8_t *)t->st_hflag.ptr, s));
+                                         (const uint8_t *)t->st_hflag.ptr, t->in_flight ? (const uint16_t *)t->st_hdone.ptr : nullptr, s));
     HIP_TRY(t, hipStreamSynchronize(s));
     return 0;
 }
@@ -1900,6 +1946,40 @@ int rg_health_read(rg_table_t *t, uint32_t first, uint32_t count, int64_t *reque
             request_success[i * F + j] = ok[j * n + i]; request_failure[i * F + j] = fl[j * n + i]; recent_failure[i * F + j] = rc[j * n + i];
         }
     return 0;
+}
+
+static int in_flight_copy(rg_table_t *t, uint32_t first, uint32_t count, uint16_t *out, const uint16_t *in, const char *who)
+{
+    if (!t) return -1;
+    if (!t->in_flight) return fail(t, -1, "%s: the table does not keep in-flight counts (rg_table_option RG_OPT_DEVICE_IN_FLIGHT is 0)", who);
+    if (!out && !in) return fail(t, -1, "%s: in_flight is NULL", who);
+    if ((uint64_t)first + count > t->G) return fail(t, -1, "%s: range exceeds %u groups", who, t->G);
+    if (count == 0) return 0;
+    if (bind(t)) return -2;
+    const size_t n = count, F = t->F, G = t->G;
+    std::vector<uint16_t> col(n * F);                       // follower-major, like the table
+    if (in)
+        for (size_t i = 0; i < n; i++)
+            for (size_t j = 0; j < F; j++) col[j * n + i] = in[i * F + j];
+    for (size_t j = 0; j < F; j++) {
+        if (in) HIP_TRY(t, hipMemcpyAsync(t->in_flight + j * G + first, col.data() + j * n, n * sizeof(uint16_t), hipMemcpyHostToDevice, t->stream));
+        else    HIP_TRY(t, hipMemcpyAsync(col.data() + j * n, t->in_flight + j * G + first, n * sizeof(uint16_t), hipMemcpyDeviceToHost, t->stream));
+    }
+    HIP_TRY(t, hipStreamSynchronize(t->stream));
+    if (out)
+        for (size_t i = 0; i < n; i++)
+            for (size_t j = 0; j < F; j++) out[i * F + j] = col[j * n + i];
+    return 0;
+}
+
+int rg_in_flight_read(rg_table_t *t, uint32_t first, uint32_t count, uint16_t *in_flight)
+{
+    return in_flight_copy(t, first, count, in_flight, nullptr, "rg_in_flight_read");
+}
+
+int rg_in_flight_set(rg_table_t *t, uint32_t first, uint32_t count, const uint16_t *in_flight)
+{
+    return in_flight_copy(t, first, count, nullptr, in_flight, "rg_in_flight_set");
 }
 
 const char *rg_step_kernel(rg_table_t *t, uint32_t count)

@@ -108,6 +108,13 @@ struct ReplicateParams {             // N1: Leader.replicateLog for many groups 
     const uint16_t *in_flight;
     rg_send_head_t *head;
     rg_send_t *send;
+    // RG_OPT_DEVICE_IN_FLIGHT (a recorded tick only; rg_replicate leaves all of it 0): counts = State.requestInFlight of the table, [F][G] like the health
+    // columns; nullptr = the option is off and `heartbeat` / `in_flight` above are the caller's columns. With it, replicate_wave derives both from the tick's own
+    // rows: ev_head / ev_out32 = its event heads and compact outcome rows, row (r, i) at r * ev_stride + i
+    uint16_t *counts;
+    const rg_ev_head_t *ev_head;
+    const I32x4 *ev_out32;
+    uint32_t ev_stride, self;
 };
 
 struct TimerParams {                 // N4: RaftRoutine.resetTimer / electionTimeout for many groups (rg_kernels.hip)
@@ -136,6 +143,7 @@ struct HealthParams {                // N4b: Leadership.State health fields + Le
     const I32x4 *out32;              // compact outcome rows instead of `reply` (rg_health_update32)
     const int64_t *now_mem;          // as TimerParams.now_mem
     int64_t now[64];
+    uint16_t *counts;                // [F][G] State.requestInFlight (RG_OPT_DEVICE_IN_FLIGHT), nullptr = off: what rg_health_failure takes one request off
 };
 
 struct TickFoldParams {              // the device-resident tick's second kernel (rg_tick2: tick_fold_kernel): timers + health + the list of fired tickets

@@ -28,8 +28,16 @@ __device__ __forceinline__ void stream_store(uint4 *dst, const uint4 v)
 // (the rows of ONE wavefront: i0 = its first row, st = its own 3 KiB of LDS; replicate_kernel and the fused tail of a recorded tick call it.
 //  stride = the rows the follower-major columns `in_flight` and `send` are laid out for: p.count, or — the sparse tick, whose row count changes from
 //  run to run while its columns stay where they are — the capacity they were sized for)
+// RG_OPT_DEVICE_IN_FLIGHT (p.counts != nullptr: a kernel argument, so the branch is the same for every lane of the grid; a recorded tick only). The per-row inputs
+// are not the caller's columns but functions of the tick's own rows: the lane walks its row's `rounds` event heads and outcome flags — what the I/O wavefront of
+// this workgroup stored behind the barrier the tail starts with, or the kernel before this one — and keeps State.requestInFlight (member/Leadership.java:31) of
+// its group's F followers in registers: zeroed by a conversion to Leader (fresh State objects), one down per ack that reached its callback
+// (Leader.java:176,221: before the result is looked at), clamped at 0; the trigger is which handler ran — an applied acceptCommand (RG_EV_CLIENT_APPEND, RG_OK,
+// RG_F_LOG_APPEND) or a Leader's onTimeout (RG_EMIT_HEARTBEAT) since the row's last conversion. One send plan per row, after the last round: a row with a command
+// sends as acceptCommand, one with a heartbeat only as onTimeout, one with neither sends NOTHING (all RG_SEND_NONE, no prepareReplication). Every follower that is
+// sent to gets +1 (Leader.java:173,217), and the F counts are stored once. One lane owns one group: plain loads and stores.
 template <int F>
-__device__ __forceinline__ void replicate_wave(const ReplicateParams &p, uint4 *st, const uint32_t i0, const uint32_t lane, const uint32_t stride)
+__device__ __forceinline__ void replicate_wave(const ReplicateParams &p, uint4 *st, const uint32_t i0, const uint32_t lane, const uint32_t stride, const uint32_t rounds)
 {
     const uint32_t i = i0 + lane;
     const bool active = i < p.count;
@@ -38,7 +46,7 @@ __device__ __forceinline__ void replicate_wave(const ReplicateParams &p, uint4 *
     const uint32_t G = p.t.groups;
     const I64x2 tc = p.t.term_commit[gi], ep = p.t.epoch[gi], w = p.t.window[gi];
     Ident id = p.t.ident[gi];
-    const bool leader = (id.meta & META_ROLE) == RG_LEADER;
+    bool leader = (id.meta & META_ROLE) == RG_LEADER;
     const int rc = (int)((id.meta >> META_RC_SHIFT) & 7u);
     const bool has_log = rc > 0;
     const int64_t first = w.x, last = w.y;
@@ -59,11 +67,43 @@ __device__ __forceinline__ void replicate_wave(const ReplicateParams &p, uint4 *
         if (rc > 2) { r2 = p.t.runs[(size_t)2 * G + gi]; }
         if (rc > 3) { r3 = p.t.runs[(size_t)3 * G + gi]; }
     }
-    const bool hb = p.heartbeat != nullptr && p.heartbeat[ir] != 0;
+    bool hb = p.heartbeat != nullptr && p.heartbeat[ir] != 0;
+    const bool derived = p.counts != nullptr;
+    uint32_t trigger = 0;                                       // RG_SENT_TRIGGERED | RG_SENT_HEARTBEAT of the row
+    if (derived) {
+#pragma unroll
+        for (int j = 0; j < F; j++) fl[j] = p.counts[(size_t)j * G + gi];
+        bool command = false, timeout = false;
+        for (uint32_t r = 0; r < rounds; r++) {
+            const size_t row = (size_t)r * p.ev_stride + ir;
+            const uint32_t flags = (uint32_t)p.ev_out32[row].y, hdr = p.ev_head[row].hdr;
+            const uint32_t kind = RG_HDR_KIND(hdr), slot = RG_HDR_SLOT(hdr), status = RG_F_STATUS(flags);
+            const bool changed = (flags & RG_F_ROLE_CHANGED) != 0;
+            if (changed) {                                      // a new participant: what the old one was about to send is gone; a new Leader has new State objects
+                command = false; timeout = false;
+                if (RG_F_ROLE(flags) == RG_LEADER) {
+#pragma unroll
+                    for (int j = 0; j < F; j++) fl[j] = 0u;
+                }
+            }
+            const bool ack = (kind == RG_EV_AE_ACK) | (kind == RG_EV_IS_ACK);
+            if (ack & !changed & (status != RG_DROPPED_STALE_ROLE) & (status != RG_BAD_EVENT) & (slot <= (uint32_t)F) & (slot != p.self)) {
+                const uint32_t jj = slot < p.self ? slot : slot - 1u;
+#pragma unroll
+                for (int j = 0; j < F; j++) fl[j] -= ((uint32_t)j == jj) & (fl[j] != 0u) ? 1u : 0u;
+            }
+            command |= (kind == RG_EV_CLIENT_APPEND) & (status == RG_OK) & ((flags & RG_F_LOG_APPEND) != 0);
+            timeout |= RG_F_EMIT(flags) == RG_EMIT_HEARTBEAT;
+        }
+        hb = timeout & !command;
+        trigger = (command | timeout) ? (hb ? (RG_SENT_TRIGGERED | RG_SENT_HEARTBEAT) : RG_SENT_TRIGGERED) : 0u;
+    }
+    const bool is_leader = leader;
+    if (derived && trigger == 0u) leader = false;               // an untriggered row plans nothing: no prepareReplication, every send RG_SEND_NONE
 
     rg_send_head_t h;
     h.term = tc.x; h.leader_commit = tc.y; h.epoch_index = ep.x; h.epoch_term = ep.y;
-    h.role_epoch = id.role_epoch; h.is_leader = leader ? 1u : 0u; h.reserved = 0;
+    h.role_epoch = id.role_epoch; h.is_leader = is_leader ? 1u : 0u; h.reserved = trigger;
 
     const uint32_t limit = hb ? RG_IN_FLIGHT_LIMIT / 10 : RG_IN_FLIGHT_LIMIT;
     const int64_t fetch = hb ? RG_REPLICATE_LIMIT / 2 : RG_REPLICATE_LIMIT;
@@ -118,6 +158,14 @@ __device__ __forceinline__ void replicate_wave(const ReplicateParams &p, uint4 *
         }
         sends[j] = s;
     }
+    if (derived & active) {                                     // +1 per request that leaves (Leader.java:173,217); the counter saturates where a uint16 ends
+#pragma unroll
+        for (int j = 0; j < F; j++) {
+            const uint32_t k = sends[j].kind;
+            const bool sent = (k == RG_SEND_APPEND) | (k == RG_SEND_SNAPSHOT) | (k == RG_SEND_NEED_HOST);
+            p.counts[(size_t)j * G + gi] = (uint16_t)(fl[j] + ((sent & (fl[j] < 0xFFFFu)) ? 1u : 0u));
+        }
+    }
 
     // ---- transposed, line-sized stores -------------------------------------------------------------------------------
     // each wavefront owns its slice of `stage`: LDS operations of one wavefront execute in order, so a wave-level
@@ -155,7 +203,7 @@ __global__ __launch_bounds__(256) void replicate_kernel(const ReplicateParams p)
 {
     __shared__ uint4 stage[4][3 * 64];                // per wavefront: 64 heads (3 x 16 B) or 64 sends (2 x 16 B)
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    replicate_wave<F>(p, stage[wave], blockIdx.x * blockDim.x + wave * 64u, lane, p.count);
+    replicate_wave<F>(p, stage[wave], blockIdx.x * blockDim.x + wave * 64u, lane, p.count, 0u);
 }
 
 #ifdef RG_TU_MAIN                   // (rg_step.hpp, "translation units": what is not a template is compiled once)
@@ -514,13 +562,20 @@ __global__ __launch_bounds__(256) void health_update_kernel(const HealthParams p
     }
 }
 
+// done: RG_OPT_DEVICE_IN_FLIGHT only (else nullptr) — the requests this call ends for the (group, follower) of entry i, summed by the host onto the FIRST entry
+// that names the pair (0 on the others), so one lane owns a counter
 __global__ __launch_bounds__(256) void health_failure_kernel(const HealthParams p, uint32_t n, const uint32_t *gid, const uint8_t *slot,
-                                                             const uint8_t *flags)
+                                                             const uint8_t *flags, const uint16_t *done)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint32_t g = gid[i], s = slot[i];
     if (g >= p.t.groups || s > p.followers || s == p.self) return;
+    if (p.counts != nullptr && done[i] != 0) {                                  // the error / timeout callback: requestInFlight-- before statFailure (Leader.java:176,221)
+        const size_t at = (size_t)(s < p.self ? s : s - 1) * p.t.groups + g;
+        const uint32_t c = p.counts[at], d = done[i];
+        p.counts[at] = (uint16_t)(c > d ? c - d : 0u);
+    }
     const uint32_t meta = p.t.ident[g].meta;
     if ((meta & META_ROLE) != RG_LEADER || !(meta & META_PREP)) return;        // no State object to land on
     const uint32_t j = s < p.self ? s : s - 1;
@@ -574,7 +629,7 @@ __global__ __launch_bounds__(256) void tick_tail_kernel(const TickTailParams p)
     const uint32_t g = blockIdx.x * 256u + threadIdx.x;
     const bool active = g < p.fp.tp.count;
     const int64_t d = active ? fold_group(p.fp, g) : 0;
-    if (p.qp.head != nullptr) replicate_wave<F>(p.qp, stage[wave], blockIdx.x * 256u + wave * 64u, lane, p.qp.count);
+    if (p.qp.head != nullptr) replicate_wave<F>(p.qp, stage[wave], blockIdx.x * 256u + wave * 64u, lane, p.qp.count, p.fp.tp.rounds);
     if (p.ready != nullptr && active) p.ready[g] = ready_of(p.rp, *p.rp.now_mem, p.critical_point, p.cool_down, g);
     if (p.fp.expire) expire_tail(p.fp, d, g, true, active, part);
 }
@@ -597,8 +652,10 @@ __global__ __launch_bounds__(2 * BLOCK) __attribute__((amdgpu_waves_per_eu(WAVES
     uint32_t *part = reinterpret_cast<uint32_t *>(smem + 3 * 64 * 16);
     // Both wavefronts map lane -> group as the step did. The tail is a chain of dependent memory round trips (a row's flags, then what they point at), not
     // work: the first wavefront folds the outcome rows into timers and health while the second plans the leaders' sends — neither reads what the other
-    // writes —; isReady needs both (the statistics, and the `prepared` mark of a leader that sent for the first time), so it comes after a meeting, on the
+    // writes. isReady needs both (the statistics, and the `prepared` mark of a leader that sent for the first time), so it comes after a meeting, on the
     // second wavefront, while the first is already in the expiry (whose first barrier the second joins when it is done).
+    // With RG_OPT_DEVICE_IN_FLIGHT the send plan depends on the rows' acks and conversions. The second wavefront does not wait for the fold: it walks its
+    // rows' heads and flags itself (replicate_wave), which the I/O wavefront stored behind the barrier above, and alone reads and writes the counts.
     const uint32_t lane = threadIdx.x & 63u;
     const bool holds = __builtin_amdgcn_readfirstlane(threadIdx.x) < (uint32_t)BLOCK;
     const uint32_t g = blockIdx.x * BLOCK + lane;
@@ -608,7 +665,7 @@ __global__ __launch_bounds__(2 * BLOCK) __attribute__((amdgpu_waves_per_eu(WAVES
     if (holds) {
         if (active) d = fold_group(tp.fp, g);
     } else {
-        if (tp.qp.head != nullptr) replicate_wave<F>(tp.qp, stage, blockIdx.x * BLOCK, lane, tp.qp.count);
+        if (tp.qp.head != nullptr) replicate_wave<F>(tp.qp, stage, blockIdx.x * BLOCK, lane, tp.qp.count, tp.fp.tp.rounds);
     }
     __syncthreads();
     if (!holds && tp.ready != nullptr && in_table) tp.ready[g] = ready_of(tp.rp, *tp.rp.now_mem, tp.critical_point, tp.cool_down, g);
@@ -689,7 +746,8 @@ __global__ __launch_bounds__(2 * BLOCK) __attribute__((amdgpu_waves_per_eu(WAVES
     __syncthreads();                                         // every store of this workgroup has landed; its LDS is free
     uint4 *stage = reinterpret_cast<uint4 *>(smem);
     // as in tick_kernel: the first wavefront folds its rows' flags into the timers and the statistics of THEIR groups while the second plans those groups' sends
-    // (neither reads what the other writes); isReady needs both, so it comes after a meeting
+    // (neither reads what the other writes); isReady needs both, so it comes after a meeting. With RG_OPT_DEVICE_IN_FLIGHT the second wavefront walks its
+    // rows' heads and flags itself (replicate_wave) and alone reads and writes the counts of the listed groups, as in tick_kernel.
     const uint32_t lane = threadIdx.x & 63u;
     const bool holds = __builtin_amdgcn_readfirstlane(threadIdx.x) < (uint32_t)BLOCK;
     const uint32_t row = blockIdx.x * BLOCK + lane;
@@ -700,7 +758,7 @@ __global__ __launch_bounds__(2 * BLOCK) __attribute__((amdgpu_waves_per_eu(WAVES
     } else if (tp.qp.head != nullptr) {
         ReplicateParams qp = tp.qp;
         qp.count = n;                                        // (the rows of this run; in_flight / send keep the capacity's layout: the stride)
-        replicate_wave<F>(qp, stage, blockIdx.x * BLOCK, lane, p0.count);
+        replicate_wave<F>(qp, stage, blockIdx.x * BLOCK, lane, p0.count, depth);
     }
     __syncthreads();
     if (!holds && tp.ready != nullptr && in_list) tp.ready[row] = ready_of(tp.rp, tp.fp.tp.now_mem[depth - 1u], tp.critical_point, tp.cool_down, g);
@@ -804,10 +862,10 @@ hipError_t launch_health_update(const HealthParams &p, hipStream_t s)
     hipLaunchKernelGGL(health_update_kernel, dim3((p.count + 255) / 256), dim3(256), 0, s, p);
     return hipGetLastError();
 }
-hipError_t launch_health_failure(const HealthParams &p, uint32_t n, const uint32_t *gid, const uint8_t *slot, const uint8_t *flags, hipStream_t s)
+hipError_t launch_health_failure(const HealthParams &p, uint32_t n, const uint32_t *gid, const uint8_t *slot, const uint8_t *flags, const uint16_t *done, hipStream_t s)
 {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(health_failure_kernel, dim3((n + 255) / 256), dim3(256), 0, s, p, n, gid, slot, flags);
+    hipLaunchKernelGGL(health_failure_kernel, dim3((n + 255) / 256), dim3(256), 0, s, p, n, gid, slot, flags, done);
     return hipGetLastError();
 }
 hipError_t launch_ready(const HealthParams &p, int64_t now, int32_t cp, int64_t cd, uint8_t *ready, hipStream_t s)

@@ -33,7 +33,7 @@ def exported_symbols():
         "rg_abi_version", "rg_table_create", "rg_table_destroy", "rg_last_error", "rg_table_groups",
         "rg_table_cluster", "rg_table_option", "rg_load_state", "rg_read_state", "rg_submit", "rg_submit32", "rg_submit32c", "rg_submit32c_sparse", "rg_submit32c_sparse_rounds", "rg_outcome32_unpack", "rg_outcome32_unpack_rel", "rg_index_base_set", "rg_index_base_get", "rg_index_base_advance", "rg_index_base_advance32", "rg_batch32_pack_rel", "rg_batch32_pack", "rg_submit_async", "rg_submit_async_packed", "rg_submit_wait", "rg_tick_create", "rg_tick_launch", "rg_tick_wait", "rg_tick_destroy", "rg_tick2_create", "rg_tick2_create_sparse", "rg_tick2_create_sparse_rounds", "rg_tick2_launch", "rg_tick2_wait", "rg_tick2_destroy", "rg_assembler_create", "rg_assemble32", "rg_assembler_destroy", "rg_timers_update32", "rg_health_update32", "rg_sync", "rg_step_kernel", "rg_host_alloc", "rg_host_free", "rg_dev_alloc",
         "rg_dev_free", "rg_copy_to_device", "rg_copy_to_host", "rg_stream", "rg_replicate", "rg_timers_configure", "rg_timers_update",
-        "rg_timers_expired", "rg_timers_expired_epochs", "rg_timers_arm", "rg_timers_read", "rg_health_update", "rg_health_failure", "rg_ready", "rg_health_read",
+        "rg_timers_expired", "rg_timers_expired_epochs", "rg_timers_arm", "rg_timers_read", "rg_health_update", "rg_health_failure", "rg_ready", "rg_health_read", "rg_in_flight_read", "rg_in_flight_set",
         "rg_timing_enable",
         "rg_timing_read", "rg_timing_begin", "rg_timing_end", "rg_counters_read", "rg_wide_body_workgroups", "rg_copy_bandwidth",
     ]
@@ -149,6 +149,8 @@ def lib():
         L.rg_health_failure.argtypes = [vp, u32, vp, vp, vp, C.c_int64]
         L.rg_ready.argtypes = [vp, C.c_int64, i32, C.c_int64, vp, i32]
         L.rg_health_read.argtypes = [vp, u32, u32, vp, vp, vp]
+        L.rg_in_flight_read.argtypes = [vp, u32, u32, vp]
+        L.rg_in_flight_set.argtypes = [vp, u32, u32, vp]
         L.rg_host_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
         L.rg_host_free.argtypes = [vp, vp]
         L.rg_dev_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
@@ -359,7 +361,9 @@ class Tick2:
     sparse_cap=N, sparse_rounds=True records the sparse tick WITH A DEPTH (rg_tick2_create_sparse_rounds): `rounds` is the greatest depth, refill takes a batch
     with a gid list and b.rounds <= rounds, writes round r of every [round][row] column at r * N and sets the count and the depth (both in page-locked host
     memory); `now` holds b.rounds clocks. outcome32() returns the b.rounds x n rows of the last refill as one contiguous [R][n] image.
-    depth_pointer=False records it without a `rounds` pointer: every refill then carries exactly `rounds` rounds."""
+    depth_pointer=False records it without a `rounds` pointer: every refill then carries exactly `rounds` rounds.
+    On a table with abi.OPT_DEVICE_IN_FLIGHT the tick is created WITHOUT the heartbeat / in_flight columns (the send step derives both from the tick's own rows and
+    the table's counts): refill then takes neither."""
 
     def __init__(self, table, rounds, entry_cap=0, expired_cap=None, send=True, ready=True, critical_point=0, cool_down_ms=0, device_resident=False, sparse_cap=None,
                  sparse_rounds=False, depth_pointer=True):
@@ -389,7 +393,9 @@ class Tick2:
         self.head, self.abcd = big(abi.HEAD_DT, rows), big(abi.QUAD32_DT, rows)
         self.entry_terms = big(np.int32, entry_cap) if entry_cap else None
         self.now = col(np.int64, rounds)
-        self.heartbeat, self.in_flight = big(np.uint8, G), big(np.uint16, F * G)      # (read by every lane of the send kernel: over the link they cost it tens of microseconds)
+        self.derived = bool(table.option(abi.OPT_DEVICE_IN_FLIGHT))
+        # (read by every lane of the send kernel: over the link they cost it tens of microseconds)
+        self.heartbeat, self.in_flight = (None, None) if self.derived else (big(np.uint8, G), big(np.uint16, F * G))
         self.row, self.persist32 = big(abi.OUT32_DT, rows), big(abi.PERSIST32_DT, rows)
         cap = table.groups if expired_cap is None else expired_cap
         self.expired_cap = cap
@@ -450,6 +456,9 @@ class Tick2:
         if b32.entry_count:
             self._put(self.entry_terms, b32.entry_terms[: b32.entry_count])
         self.now[:] = np.asarray(now, dtype=np.int64)
+        if self.derived:
+            assert heartbeat is None and in_flight is None, "a table with OPT_DEVICE_IN_FLIGHT derives both"
+            return
         if heartbeat is not None or not isinstance(self.heartbeat, DeviceBuffer):
             self._put(self.heartbeat, np.zeros(self.G, np.uint8) if heartbeat is None else np.ascontiguousarray(heartbeat, dtype=np.uint8))
         if in_flight is not None or not isinstance(self.in_flight, DeviceBuffer):
@@ -478,12 +487,15 @@ class Tick2:
         if b32.entry_count:
             self._put(self.entry_terms, b32.entry_terms[: b32.entry_count])
         self._clocks(now)
+        self.count[0] = n
+        self.n = n
+        if self.derived:
+            assert heartbeat is None and in_flight is None, "a table with OPT_DEVICE_IN_FLIGHT derives both"
+            return
         self._put(self.heartbeat, np.zeros(n, np.uint8) if heartbeat is None else np.ascontiguousarray(heartbeat, dtype=np.uint8).reshape(n))
         fl = np.zeros((self.F, n), np.uint16) if in_flight is None else np.ascontiguousarray(np.asarray(in_flight, dtype=np.uint16).reshape(self.F, n))
         for j in range(self.F):                            # element (j, row) at j * capacity + row
             self._put(self.in_flight, fl[j], at=j * self.G)
-        self.count[0] = n
-        self.n = n
 
     def launch(self):
         self.table._check(lib().rg_tick2_launch(self._h))
@@ -729,6 +741,7 @@ class Table:
 
     def __init__(self, groups, cluster, self_slot=0, pre_vote=True, device=0):
         self.groups, self.cluster, self.self_slot, self.pre_vote, self.device = groups, cluster, self_slot, pre_vote, device
+        self._options = {}
         h = C.c_void_p()
         rc = lib().rg_table_create(device, groups, cluster, self_slot, int(pre_vote), C.byref(h))
         if rc:
@@ -774,6 +787,32 @@ class Table:
     def set_option(self, option, value):
         """rg_table_option, e.g. (abi.OPT_REQUIRE_FENCED_TIMEOUTS, 1)"""
         self._check(lib().rg_table_option(self._h, option, int(value)))
+        # (remembered only when the library took it; RG_OPT_REQUIRE_FENCED_TIMEOUTS is a flag: the library reads any non-zero value as 1)
+        self._options[option] = int(value) if option != abi.OPT_REQUIRE_FENCED_TIMEOUTS else int(value != 0)
+
+    def option(self, option):
+        """the value THIS OBJECT last set for `option` through set_option (0, every option's default, when it never did). The C ABI has no getter, so this is a
+        record kept in Python, not the table's state: an option set on the handle through lib() directly is not seen here. Tick2 decides from it whether to
+        allocate the heartbeat / in_flight columns; for a table whose RG_OPT_DEVICE_IN_FLIGHT was switched on behind this object's back it allocates them and
+        the library refuses the tick (rg_tick2_create*: -1, a message that names the option), which is the safe direction."""
+        return self._options.get(option, 0)
+
+    def set_device_in_flight(self, on=True):
+        """rg_table_option(RG_OPT_DEVICE_IN_FLIGHT): the table keeps State.requestInFlight per (group, follower) and the send step of a Tick2 created afterwards
+        derives heartbeat / in_flight from its own rows; off (the default) the tick reads the caller's columns"""
+        self.set_option(abi.OPT_DEVICE_IN_FLIGHT, 1 if on else 0)
+
+    def in_flight_read(self, first=0, count=None):
+        """rg_in_flight_read -> uint16[count, cluster - 1]"""
+        count = self.groups - first if count is None else count
+        out = np.zeros((count, self.cluster - 1), np.uint16)
+        self._check(lib().rg_in_flight_read(self._h, first, count, out.ctypes.data))
+        return out
+
+    def in_flight_set(self, in_flight, first=0):
+        """rg_in_flight_set: in_flight is [count, cluster - 1]"""
+        a = np.ascontiguousarray(np.asarray(in_flight, dtype=np.uint16).reshape(-1, self.cluster - 1))
+        self._check(lib().rg_in_flight_set(self._h, first, len(a), a.ctypes.data))
 
     # state ---------------------------------------------------------------------------------------
     def load_state(self, state, first=0):
