@@ -19,27 +19,6 @@
 #include "rg_device.hpp"
 #include "rg_assemble.hpp"
 
-namespace rg {
-hipError_t launch_step(const StepParams &p, int followers, bool sparse, int shape, hipStream_t s);
-hipError_t launch_copy(const void *src, void *dst, size_t bytes, hipStream_t s);
-hipError_t launch_replicate(const ReplicateParams &p, int followers, hipStream_t s);
-hipError_t launch_health_update(const HealthParams &p, hipStream_t s);
-hipError_t launch_health_failure(const HealthParams &p, uint32_t n, const uint32_t *gid, const uint8_t *slot, const uint8_t *flags, const uint16_t *done, hipStream_t s);
-hipError_t launch_ready(const HealthParams &p, int64_t now, int32_t cp, int64_t cd, uint8_t *ready, hipStream_t s);
-hipError_t launch_timers_update(const TimerParams &p, hipStream_t s);
-hipError_t launch_tick_fold(const TickFoldParams &p, hipStream_t s);
-hipError_t launch_tick_tail(const TickTailParams &p, int followers, hipStream_t s);
-hipError_t launch_tick(const StepParams &p, const TickTailParams &tp, int followers, hipStream_t s);
-hipError_t launch_tick_sparse(const StepParams &p, const TickTailParams &tp, const uint32_t *rows_now, int followers, hipStream_t s);
-hipError_t launch_tick_expire(const TickFoldParams &p, hipStream_t s);
-hipError_t launch_timers_arm(const TimerParams &p, hipStream_t s);
-hipError_t launch_timers_expired(int64_t *deadline, const Ident *ident, uint32_t groups, int64_t now, const int64_t *now_mem, uint32_t *counts, uint32_t *total,
-                                 uint32_t *out_gid, uint32_t *out_epoch, uint32_t capacity, hipStream_t s);
-hipError_t launch_outcome_count(const rg_reply_t *reply, uint32_t rows, uint32_t *counts, uint32_t *totals, hipStream_t s);
-hipError_t launch_outcome_emit(const rg_reply_t *reply, const I64x2 *logfx, const rg_persist_t *persist, uint32_t rows, const uint32_t *counts,
-                               I64x2 *out_logfx, uint32_t cap_logfx, rg_persist_t *out_persist, uint32_t cap_persist, hipStream_t s);
-}  // namespace rg
-
 using rg::DevTable;
 using rg::I64x2;
 
@@ -881,19 +860,19 @@ int rg_tick2_destroy(rg_tick2_t *k)
 
 // the device's address of memory the caller says is device-visible: page-locked host memory is mapped, device memory is what it is; pageable host
 // memory (which a kernel would fault on) is refused where the runtime can tell
-static int device_visible(rg_table *t, const void *p, const char *what, void **out)
+static int device_visible(rg_table *t, const char *who, const void *p, const char *what, void **out)
 {
     *out = nullptr;
     if (!p) return 0;
     hipPointerAttribute_t a{};
     if (hipPointerGetAttributes(&a, p) != hipSuccess || a.type == hipMemoryTypeUnregistered) {
         (void)hipGetLastError();
-        return fail(t, -1, "rg_tick2_create: %s is neither device memory (rg_dev_alloc) nor page-locked host memory (rg_host_alloc)", what);
+        return fail(t, -1, "%s: %s is neither device memory (rg_dev_alloc) nor page-locked host memory (rg_host_alloc)", who, what);
     }
     if (a.type == hipMemoryTypeHost) {
         if (hipHostGetDevicePointer(out, const_cast<void *>(p), 0) != hipSuccess) {
             (void)hipGetLastError();
-            return fail(t, -1, "rg_tick2_create: %s is host memory the device cannot address", what);
+            return fail(t, -1, "%s: %s is host memory the device cannot address", who, what);
         }
         return 0;
     }
@@ -933,13 +912,14 @@ static int tick2_create(rg_table_t *t, const rg_tick2_io_t *io, const rg_tick2_r
     const rg_outcome_t shape{&dummy_r, &dummy_l, &dummy_p};
     if (int rc = check_batch(t, &wide, &shape, false, deep)) return rc;
     if (bind(t)) return -2;
+    const auto visible = [t](const void *p, const char *what, void **out) { return device_visible(t, "rg_tick2_create", p, what, out); };      // (whichever constructor: the refusals have always said rg_tick2_create)
     void *d_head, *d_abcd, *d_terms, *d_now, *d_hb, *d_fl, *d_row, *d_per, *d_egid, *d_eep, *d_ecnt, *d_sh, *d_ss, *d_ready, *d_gid = nullptr, *d_cnt = nullptr, *d_depth = nullptr;
-    if ((rows && (device_visible(t, rows->gid, "gid", &d_gid) || device_visible(t, rows->count, "count", &d_cnt) || device_visible(t, depth_now, "rounds", &d_depth))) ||
-        device_visible(t, io->head, "head", &d_head) || device_visible(t, io->abcd, "abcd", &d_abcd) || device_visible(t, io->entry_terms, "entry_terms", &d_terms) ||
-        device_visible(t, io->now, "now", &d_now) || device_visible(t, io->heartbeat, "heartbeat", &d_hb) || device_visible(t, io->in_flight, "in_flight", &d_fl) ||
-        device_visible(t, io->row, "row", &d_row) || device_visible(t, io->persist32, "persist32", &d_per) || device_visible(t, io->expired_gid, "expired_gid", &d_egid) ||
-        device_visible(t, io->expired_epoch, "expired_epoch", &d_eep) || device_visible(t, io->expired_count, "expired_count", &d_ecnt) ||
-        device_visible(t, io->send_head, "send_head", &d_sh) || device_visible(t, io->send, "send", &d_ss) || device_visible(t, io->ready, "ready", &d_ready))
+    if ((rows && (visible(rows->gid, "gid", &d_gid) || visible(rows->count, "count", &d_cnt) || visible(depth_now, "rounds", &d_depth))) ||
+        visible(io->head, "head", &d_head) || visible(io->abcd, "abcd", &d_abcd) || visible(io->entry_terms, "entry_terms", &d_terms) ||
+        visible(io->now, "now", &d_now) || visible(io->heartbeat, "heartbeat", &d_hb) || visible(io->in_flight, "in_flight", &d_fl) ||
+        visible(io->row, "row", &d_row) || visible(io->persist32, "persist32", &d_per) || visible(io->expired_gid, "expired_gid", &d_egid) ||
+        visible(io->expired_epoch, "expired_epoch", &d_eep) || visible(io->expired_count, "expired_count", &d_ecnt) ||
+        visible(io->send_head, "send_head", &d_sh) || visible(io->send, "send", &d_ss) || visible(io->ready, "ready", &d_ready))
         return -1;
     rg_tick2 *k = new rg_tick2();
     k->t = t;
@@ -1121,27 +1101,6 @@ int rg_assembler_create(rg_table_t *t, uint32_t max_events, uint32_t max_expired
     return 0;
 }
 
-// device_visible() under the caller's name: the device's address of `p`, or a refusal
-static int asm_visible(rg_table *t, const void *p, const char *what, void **out)
-{
-    *out = nullptr;
-    if (!p) return 0;
-    hipPointerAttribute_t at{};
-    if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type == hipMemoryTypeUnregistered) {
-        (void)hipGetLastError();
-        return fail(t, -1, "rg_assemble32: %s is neither device memory (rg_dev_alloc) nor page-locked host memory (rg_host_alloc)", what);
-    }
-    if (at.type == hipMemoryTypeHost) {
-        if (hipHostGetDevicePointer(out, const_cast<void *>(p), 0) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(t, -1, "rg_assemble32: %s is host memory the device cannot address", what);
-        }
-        return 0;
-    }
-    *out = const_cast<void *>(p);
-    return 0;
-}
-
 int rg_assemble32(rg_assembler_t *a, const rg_arrivals_t *in, const rg_assembled_t *out, int memspace)
 {
     if (!a || !a->t) return -1;
@@ -1171,7 +1130,7 @@ int rg_assemble32(rg_assembler_t *a, const rg_arrivals_t *in, const rg_assembled
             {in->expired_count, "expired_count"}, {out->gid, "the batch's gid"}, {out->count, "the batch's count"}, {out->rounds, "rounds"}, {out->head, "the batch's head"},
             {out->abcd, "the batch's abcd"}, {out->origin, "origin"}, {out->deferred, "deferred"}, {out->stats, "stats"}};
         int k = 0;
-        for (const auto &c : cols) if (int rc = asm_visible(t, c.ptr, c.what, &v[k++])) return rc;
+        for (const auto &c : cols) if (int rc = device_visible(t, "rg_assemble32", c.ptr, c.what, &v[k++])) return rc;
         p.in_count = (const uint32_t *)v[0]; p.in_gid = (const uint32_t *)v[1]; p.in_head = (const rg::U32x2 *)v[2]; p.in_abcd = (const rg::I32x4 *)v[3];
         p.ex_gid = (const uint32_t *)v[4]; p.ex_epoch = (const uint32_t *)v[5]; p.ex_count = (const uint32_t *)v[6];
         p.gid = (uint32_t *)v[7]; p.count = (uint32_t *)v[8]; p.rounds = (uint32_t *)v[9]; p.head = (rg::U32x2 *)v[10]; p.abcd = (rg::I32x4 *)v[11];

@@ -167,6 +167,27 @@ struct TickTailParams {              // everything a recorded tick does after th
     uint8_t *ready;                  // nullptr: no readiness column
 };
 
+// The launchers: defined in rg_kernels.hip, called by raftgpu.cpp (launch_assemble: rg_assemble.hpp). Declared here for both, so that a definition that drifts
+// from its declaration does not compile.
+hipError_t launch_step(const StepParams &p, int followers, bool sparse, int shape, hipStream_t s);
+hipError_t launch_copy(const void *src, void *dst, size_t bytes, hipStream_t s);
+hipError_t launch_replicate(const ReplicateParams &p, int followers, hipStream_t s);
+hipError_t launch_health_update(const HealthParams &p, hipStream_t s);
+hipError_t launch_health_failure(const HealthParams &p, uint32_t n, const uint32_t *gid, const uint8_t *slot, const uint8_t *flags, const uint16_t *done, hipStream_t s);
+hipError_t launch_ready(const HealthParams &p, int64_t now, int32_t cp, int64_t cd, uint8_t *ready, hipStream_t s);
+hipError_t launch_timers_update(const TimerParams &p, hipStream_t s);
+hipError_t launch_tick_fold(const TickFoldParams &p, hipStream_t s);
+hipError_t launch_tick_tail(const TickTailParams &p, int followers, hipStream_t s);
+hipError_t launch_tick(const StepParams &p, const TickTailParams &tp, int followers, hipStream_t s);
+hipError_t launch_tick_sparse(const StepParams &p, const TickTailParams &tp, const uint32_t *rows_now, int followers, hipStream_t s);
+hipError_t launch_tick_expire(const TickFoldParams &p, hipStream_t s);
+hipError_t launch_timers_arm(const TimerParams &p, hipStream_t s);
+hipError_t launch_timers_expired(int64_t *deadline, const Ident *ident, uint32_t groups, int64_t now, const int64_t *now_mem, uint32_t *counts, uint32_t *total,
+                                 uint32_t *out_gid, uint32_t *out_epoch, uint32_t capacity, hipStream_t s);
+hipError_t launch_outcome_count(const rg_reply_t *reply, uint32_t rows, uint32_t *counts, uint32_t *totals, hipStream_t s);
+hipError_t launch_outcome_emit(const rg_reply_t *reply, const I64x2 *logfx, const rg_persist_t *persist, uint32_t rows, const uint32_t *counts,
+                               I64x2 *out_logfx, uint32_t cap_logfx, rg_persist_t *out_persist, uint32_t cap_persist, hipStream_t s);
+
 __device__ __forceinline__ int64_t wadd(int64_t a, int64_t b) { return (int64_t)((uint64_t)a + (uint64_t)b); }
 __device__ __forceinline__ int64_t wsub(int64_t a, int64_t b) { return (int64_t)((uint64_t)a - (uint64_t)b); }
 __device__ __forceinline__ int64_t max64(int64_t a, int64_t b) { return a > b ? a : b; }

@@ -206,26 +206,19 @@ __global__ __launch_bounds__(256) void replicate_kernel(const ReplicateParams p)
     replicate_wave<F>(p, stage[wave], blockIdx.x * blockDim.x + wave * 64u, lane, p.count, 0u);
 }
 
-#ifdef RG_TU_MAIN                   // (rg_step.hpp, "translation units": what is not a template is compiled once)
-hipError_t launch_replicate(const ReplicateParams &p, int followers, hipStream_t s)
-{
-    const uint32_t blocks = (p.count + 255) / 256;
-    if (blocks == 0) return hipSuccess;
-    switch (followers) {
-    case 1: hipLaunchKernelGGL(replicate_kernel<1>, dim3(blocks), dim3(256), 0, s, p); break;
-    case 2: hipLaunchKernelGGL(replicate_kernel<2>, dim3(blocks), dim3(256), 0, s, p); break;
-    case 3: hipLaunchKernelGGL(replicate_kernel<3>, dim3(blocks), dim3(256), 0, s, p); break;
-    case 4: hipLaunchKernelGGL(replicate_kernel<4>, dim3(blocks), dim3(256), 0, s, p); break;
-    case 5: hipLaunchKernelGGL(replicate_kernel<5>, dim3(blocks), dim3(256), 0, s, p); break;
-    case 6: hipLaunchKernelGGL(replicate_kernel<6>, dim3(blocks), dim3(256), 0, s, p); break;
-#define RG_REPLICATE_CASE(F_) case F_: hipLaunchKernelGGL(replicate_kernel<F_>, dim3(blocks), dim3(256), 0, s, p); break;
-    RG_REPLICATE_CASE(7) RG_REPLICATE_CASE(8) RG_REPLICATE_CASE(9) RG_REPLICATE_CASE(10) RG_REPLICATE_CASE(11) RG_REPLICATE_CASE(12) RG_REPLICATE_CASE(13) RG_REPLICATE_CASE(14)
-#undef RG_REPLICATE_CASE
-    default: return hipErrorInvalidValue;
+struct ReplicateLaunch {
+    const ReplicateParams &p;
+    hipStream_t s;
+    template <int F> hipError_t run() const
+    {
+        const ReplicateParams &p = this->p;
+        const hipStream_t s = this->s;
+        const uint32_t blocks = (p.count + 255) / 256;
+        if (blocks == 0) return hipSuccess;
+        hipLaunchKernelGGL(replicate_kernel<F>, dim3(blocks), dim3(256), 0, s, p);
+        return hipGetLastError();
     }
-    return hipGetLastError();
-}
-#endif
+};
 
 // ---- N4: timers ------------------------------------------------------------------------------------------
 __host__ __device__ __forceinline__ uint64_t timer_mix(uint64_t x)
@@ -671,51 +664,24 @@ __global__ __launch_bounds__(2 * BLOCK) __attribute__((amdgpu_waves_per_eu(WAVES
     if (!holds && tp.ready != nullptr && in_table) tp.ready[g] = ready_of(tp.rp, *tp.rp.now_mem, tp.critical_point, tp.cool_down, g);
     if (tp.fp.expire) expire_tail(tp.fp, d, g, holds, active, part);
 }
-// 7 .. 14 followers (a table with RG_OPT_COMPACT_ANY_CLUSTER): one register budget, as for the step kernels (rg_step.hpp: launch_compact_big), and launchers over
-// a range of four follower counts that may have a translation unit of their own (rg_step.hpp, "translation units"); F = 0: not in this build
-template <int F>
-static hipError_t launch_tick_big(const StepParams &p, const TickTailParams &tp, const dim3 grid, hipStream_t s)
-{
-    if constexpr (F == 0) return hipErrorInvalidValue;
-    else { hipLaunchKernelGGL((tick_kernel<F, 1>), grid, dim3(2 * BLOCK), 0, s, p, tp); return hipGetLastError(); }
-}
-template <int LO>
-hipError_t launch_tick_range(const StepParams &p, const TickTailParams &tp, int followers, const dim3 grid, hipStream_t s)
-{
-    switch (followers - LO) {
-    case 0: return launch_tick_big<RG_BIG_F(LO)>(p, tp, grid, s);
-    case 1: return launch_tick_big<RG_BIG_F(LO + 1)>(p, tp, grid, s);
-    case 2: return launch_tick_big<RG_BIG_F(LO + 2)>(p, tp, grid, s);
-    case 3: return launch_tick_big<RG_BIG_F(LO + 3)>(p, tp, grid, s);
-    default: return hipErrorInvalidValue;
+struct TickLaunch {
+    const StepParams &p;
+    const TickTailParams &tp;
+    hipStream_t s;
+    template <int F> hipError_t run() const
+    {
+        const StepParams &p = this->p;
+        const TickTailParams &tp = this->tp;
+        const hipStream_t s = this->s;
+        const uint32_t blocks = (p.count + BLOCK - 1) / BLOCK;
+        if (blocks == 0) return hipSuccess;
+        if (p.count >= (1u << 28) || p.out32 == nullptr || p.force_wide != 0) return hipErrorInvalidValue;
+        const dim3 grid(blocks), wg(2 * BLOCK);
+        if (blocks > MANY_BLOCKS) hipLaunchKernelGGL((tick_kernel<F, WAVES_MANY<F>>), grid, wg, 0, s, p, tp);      // (the register budgets: rg_step.hpp, WAVES_MANY)
+        else                      hipLaunchKernelGGL((tick_kernel<F, 1>), grid, wg, 0, s, p, tp);
+        return hipGetLastError();
     }
-}
-#define RG_TICK_RANGE(LO_) hipError_t launch_tick_range<LO_>(const StepParams &, const TickTailParams &, int, const dim3, hipStream_t)
-#if defined(RG_TU) && RG_TU == 1
-extern template RG_TICK_RANGE(7); extern template RG_TICK_RANGE(11);
-#elif defined(RG_TU)
-template RG_TICK_RANGE(RG_TU);
-#endif
-#undef RG_TICK_RANGE
-#ifdef RG_TU_MAIN
-hipError_t launch_tick(const StepParams &p, const TickTailParams &tp, int followers, hipStream_t s)
-{
-    const uint32_t blocks = (p.count + BLOCK - 1) / BLOCK;
-    if (blocks == 0) return hipSuccess;
-    if (p.count >= (1u << 28) || p.out32 == nullptr || p.force_wide != 0) return hipErrorInvalidValue;
-    const bool many = blocks > 1024u;
-    const dim3 grid(blocks), wg(2 * BLOCK);
-    switch (followers) {
-#define RG_TICK_CASE(F_) case F_: if (many) hipLaunchKernelGGL((tick_kernel<F_, 4>), grid, wg, 0, s, p, tp); else hipLaunchKernelGGL((tick_kernel<F_, 1>), grid, wg, 0, s, p, tp); break;
-    RG_TICK_CASE(1) RG_TICK_CASE(2) RG_TICK_CASE(3) RG_TICK_CASE(4) RG_TICK_CASE(5) RG_TICK_CASE(6)
-#undef RG_TICK_CASE
-    case 7: case 8: case 9: case 10: return launch_tick_range<7>(p, tp, followers, grid, s);
-    case 11: case 12: case 13: case 14: return launch_tick_range<11>(p, tp, followers, grid, s);
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-#endif
+};
 // ---- the SPARSE recorded tick (rg_tick2_create_sparse): the same for a LIST of groups whose length changes from run to run --------------------------------
 // Most groups of a 100-us tick have no event, and tick_kernel reads and writes all of them all the same. Here a workgroup is 64 ROWS: row i of every per-row
 // column belongs to group gid[i], the columns are sized for p0.count = the tick's capacity, and the rows of THIS run — n = min(*rows_now, capacity) — are read
@@ -763,51 +729,39 @@ __global__ __launch_bounds__(2 * BLOCK) __attribute__((amdgpu_waves_per_eu(WAVES
     __syncthreads();
     if (!holds && tp.ready != nullptr && in_list) tp.ready[row] = ready_of(tp.rp, tp.fp.tp.now_mem[depth - 1u], tp.critical_point, tp.cool_down, g);
 }
-template <int F>
-static hipError_t launch_tick_sparse_big(const StepParams &p, const TickTailParams &tp, const uint32_t *rows_now, const dim3 grid, hipStream_t s)
-{
-    if constexpr (F == 0) return hipErrorInvalidValue;
-    else { hipLaunchKernelGGL((tick_sparse_kernel<F, 1>), grid, dim3(2 * BLOCK), 0, s, p, tp, rows_now); return hipGetLastError(); }
-}
-template <int F>
-static hipError_t launch_tick_tail_big(const TickTailParams &p, const dim3 grid, hipStream_t s)
-{
-    if constexpr (F == 0) return hipErrorInvalidValue;
-    else { hipLaunchKernelGGL(tick_tail_kernel<F>, grid, dim3(256), 0, s, p); return hipGetLastError(); }
-}
-template <int LO>
-hipError_t launch_tick_sparse_range(const StepParams &p, const TickTailParams &tp, const uint32_t *rows_now, int followers, const dim3 grid, hipStream_t s)
-{
-    switch (followers - LO) {
-    case 0: return launch_tick_sparse_big<RG_BIG_F(LO)>(p, tp, rows_now, grid, s);
-    case 1: return launch_tick_sparse_big<RG_BIG_F(LO + 1)>(p, tp, rows_now, grid, s);
-    case 2: return launch_tick_sparse_big<RG_BIG_F(LO + 2)>(p, tp, rows_now, grid, s);
-    case 3: return launch_tick_sparse_big<RG_BIG_F(LO + 3)>(p, tp, rows_now, grid, s);
-    default: return hipErrorInvalidValue;
+// p.count = the capacity (1 .. groups): what the per-row columns are sized for, and the grid
+struct TickSparseLaunch {
+    const StepParams &p;
+    const TickTailParams &tp;
+    const uint32_t *rows_now;
+    hipStream_t s;
+    template <int F> hipError_t run() const
+    {
+        const StepParams &p = this->p;
+        const TickTailParams &tp = this->tp;
+        const uint32_t *rows_now = this->rows_now;
+        const hipStream_t s = this->s;
+        const uint32_t blocks = (p.count + BLOCK - 1) / BLOCK;
+        if (blocks == 0 || p.count >= (1u << 28) || p.out32 == nullptr || p.gid == nullptr || rows_now == nullptr || p.rounds == 0u || p.rounds > 64u || p.stride != p.count || tp.fp.tp.rounds != p.rounds) return hipErrorInvalidValue;
+        const dim3 grid(blocks), wg(2 * BLOCK);
+        if (blocks > MANY_BLOCKS) hipLaunchKernelGGL((tick_sparse_kernel<F, WAVES_MANY<F>>), grid, wg, 0, s, p, tp, rows_now);
+        else                      hipLaunchKernelGGL((tick_sparse_kernel<F, 1>), grid, wg, 0, s, p, tp, rows_now);
+        return hipGetLastError();
     }
-}
-template <int LO>
-hipError_t launch_tick_tail_range(const TickTailParams &p, int followers, const dim3 grid, hipStream_t s)
-{
-    switch (followers - LO) {
-    case 0: return launch_tick_tail_big<RG_BIG_F(LO)>(p, grid, s);
-    case 1: return launch_tick_tail_big<RG_BIG_F(LO + 1)>(p, grid, s);
-    case 2: return launch_tick_tail_big<RG_BIG_F(LO + 2)>(p, grid, s);
-    case 3: return launch_tick_tail_big<RG_BIG_F(LO + 3)>(p, grid, s);
-    default: return hipErrorInvalidValue;
+};
+struct TickTailLaunch {
+    const TickTailParams &p;
+    hipStream_t s;
+    template <int F> hipError_t run() const
+    {
+        const TickTailParams &p = this->p;
+        const hipStream_t s = this->s;
+        const uint32_t blocks = (p.fp.tp.count + 255) / 256;
+        if (blocks == 0) return hipSuccess;
+        hipLaunchKernelGGL(tick_tail_kernel<F>, dim3(blocks), dim3(256), 0, s, p);
+        return hipGetLastError();
     }
-}
-#define RG_SPARSE_RANGE(LO_) hipError_t launch_tick_sparse_range<LO_>(const StepParams &, const TickTailParams &, const uint32_t *, int, const dim3, hipStream_t)
-#define RG_TAIL_RANGE(LO_) hipError_t launch_tick_tail_range<LO_>(const TickTailParams &, int, const dim3, hipStream_t)
-#if defined(RG_TU) && RG_TU == 1
-extern template RG_SPARSE_RANGE(7); extern template RG_SPARSE_RANGE(11);
-extern template RG_TAIL_RANGE(7); extern template RG_TAIL_RANGE(11);
-#elif defined(RG_TU)
-template RG_SPARSE_RANGE(RG_TU);
-template RG_TAIL_RANGE(RG_TU);
-#endif
-#undef RG_SPARSE_RANGE
-#undef RG_TAIL_RANGE
+};
 #ifdef RG_TU_MAIN
 // the fired tickets of the whole table at the clock of the run's last round, now[R - 1], one lane per group: the sparse tick's second node (expire_tail as the dense kernels call it)
 __global__ __launch_bounds__(256) void tick_expire_kernel(const TickFoldParams p)
@@ -818,41 +772,10 @@ __global__ __launch_bounds__(256) void tick_expire_kernel(const TickFoldParams p
     const int64_t d = active ? p.tp.deadline[g] : 0;
     expire_tail(p, p.tp.now_mem[tick_depth(p) - 1u], d, g, true, active, part);
 }
-// p.count = the capacity (1 .. groups): what the per-row columns are sized for, and the grid
-hipError_t launch_tick_sparse(const StepParams &p, const TickTailParams &tp, const uint32_t *rows_now, int followers, hipStream_t s)
-{
-    const uint32_t blocks = (p.count + BLOCK - 1) / BLOCK;
-    if (blocks == 0 || p.count >= (1u << 28) || p.out32 == nullptr || p.gid == nullptr || rows_now == nullptr || p.rounds == 0u || p.rounds > 64u || p.stride != p.count || tp.fp.tp.rounds != p.rounds) return hipErrorInvalidValue;
-    const bool many = blocks > 1024u;
-    const dim3 grid(blocks), wg(2 * BLOCK);
-    switch (followers) {
-#define RG_TICK_CASE(F_) case F_: if (many) hipLaunchKernelGGL((tick_sparse_kernel<F_, 4>), grid, wg, 0, s, p, tp, rows_now); else hipLaunchKernelGGL((tick_sparse_kernel<F_, 1>), grid, wg, 0, s, p, tp, rows_now); break;
-    RG_TICK_CASE(1) RG_TICK_CASE(2) RG_TICK_CASE(3) RG_TICK_CASE(4) RG_TICK_CASE(5) RG_TICK_CASE(6)
-#undef RG_TICK_CASE
-    case 7: case 8: case 9: case 10: return launch_tick_sparse_range<7>(p, tp, rows_now, followers, grid, s);
-    case 11: case 12: case 13: case 14: return launch_tick_sparse_range<11>(p, tp, rows_now, followers, grid, s);
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
 hipError_t launch_tick_expire(const TickFoldParams &p, hipStream_t s)
 {
     if (p.tp.groups == 0) return hipSuccess;
     hipLaunchKernelGGL(tick_expire_kernel, dim3((p.tp.groups + 255) / 256), dim3(256), 0, s, p);
-    return hipGetLastError();
-}
-hipError_t launch_tick_tail(const TickTailParams &p, int followers, hipStream_t s)
-{
-    const uint32_t blocks = (p.fp.tp.count + 255) / 256;
-    if (blocks == 0) return hipSuccess;
-    switch (followers) {
-#define RG_TAIL_CASE(F_) case F_: hipLaunchKernelGGL(tick_tail_kernel<F_>, dim3(blocks), dim3(256), 0, s, p); break;
-    RG_TAIL_CASE(1) RG_TAIL_CASE(2) RG_TAIL_CASE(3) RG_TAIL_CASE(4) RG_TAIL_CASE(5) RG_TAIL_CASE(6)
-#undef RG_TAIL_CASE
-    case 7: case 8: case 9: case 10: return launch_tick_tail_range<7>(p, followers, dim3(blocks), s);
-    case 11: case 12: case 13: case 14: return launch_tick_tail_range<11>(p, followers, dim3(blocks), s);
-    default: return hipErrorInvalidValue;
-    }
     return hipGetLastError();
 }
 
@@ -954,6 +877,30 @@ hipError_t launch_copy(const void *src, void *dst, size_t bytes, hipStream_t s)
     return hipGetLastError();
 }
 
+#endif
+
+// ---- the families launched by follower count (rg_step.hpp, "launches by follower count"): their ranges of 7 .. 14 followers, per translation unit, and their entry points
+// (ReplicateLaunch is not on the list: a launcher that is not keeps its ranges in the main unit, instantiated where they are used. replicate_kernel compiles in
+//  seconds, and next to the step kernels of a range unit the allocator hands replicate_kernel<11 .. 14> other registers than the ones that were measured.)
+#define RG_FOLLOWER_LAUNCHERS(X) X(StepLaunch) X(TickLaunch) X(TickSparseLaunch) X(TickTailLaunch)
+#if defined(RG_TU) && RG_TU == 1
+#define RG_PER_UNIT(L) extern template hipError_t launch_range<L, 7>(const L &, int); extern template hipError_t launch_range<L, 11>(const L &, int);
+#elif defined(RG_TU)
+#define RG_PER_UNIT(L) template hipError_t launch_range<L, RG_TU>(const L &, int);
+#else
+#define RG_PER_UNIT(L)
+#endif
+RG_FOLLOWER_LAUNCHERS(RG_PER_UNIT)
+#undef RG_PER_UNIT
+#ifdef RG_TU_MAIN
+hipError_t launch_step(const StepParams &p, int followers, bool sparse, int shape, hipStream_t s) { return launch_followers(StepLaunch{p, sparse, shape, s}, followers); }
+hipError_t launch_replicate(const ReplicateParams &p, int followers, hipStream_t s) { return launch_followers(ReplicateLaunch{p, s}, followers); }
+hipError_t launch_tick(const StepParams &p, const TickTailParams &tp, int followers, hipStream_t s) { return launch_followers(TickLaunch{p, tp, s}, followers); }
+hipError_t launch_tick_sparse(const StepParams &p, const TickTailParams &tp, const uint32_t *rows_now, int followers, hipStream_t s)
+{
+    return launch_followers(TickSparseLaunch{p, tp, rows_now, s}, followers);
+}
+hipError_t launch_tick_tail(const TickTailParams &p, int followers, hipStream_t s) { return launch_followers(TickTailLaunch{p, s}, followers); }
 #endif
 
 }  // namespace rg

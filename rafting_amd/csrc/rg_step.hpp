@@ -1208,180 +1208,123 @@ __global__ __launch_bounds__(2 * BLOCK) __attribute__((amdgpu_waves_per_eu(WAVES
     split_body<F, SPARSE, true, OUT32>(p, smem);
 }
 
-template <int F>
-static hipError_t launch_single(const StepParams &p, bool sparse, hipStream_t s)
-{
-    const uint32_t blocks = (p.count + BLOCK - 1) / BLOCK;
-    if (blocks == 0) return hipSuccess;
-    if (sparse) hipLaunchKernelGGL((step_kernel<F, true>), dim3(blocks), dim3(BLOCK), 0, s, p);
-    else        hipLaunchKernelGGL((step_kernel<F, false>), dim3(blocks), dim3(BLOCK), 0, s, p);
-    return hipGetLastError();
-}
-
-template <int F>
-static hipError_t launch_split(const StepParams &p, bool sparse, hipStream_t s)
-{
-    const uint32_t blocks = (p.count + BLOCK - 1) / BLOCK;
-    if (blocks == 0) return hipSuccess;
-    if (sparse) hipLaunchKernelGGL((step_split_kernel<F, true>), dim3(blocks), dim3(2 * BLOCK), 0, s, p);
-    else        hipLaunchKernelGGL((step_split_kernel<F, false>), dim3(blocks), dim3(2 * BLOCK), 0, s, p);
-    return hipGetLastError();
-}
-
-template <int F>
-static hipError_t launch_compact(const StepParams &p, bool sparse, hipStream_t s)
-{
-    const uint32_t blocks = (p.count + BLOCK - 1) / BLOCK;
-    if (blocks == 0) return hipSuccess;
-    if (p.count >= (1u << 28)) return hipErrorInvalidValue;       // the I/O wavefront addresses a row as scalar base + 32-bit lane offset
-    const bool many = blocks > 1024u;                    // more than one workgroup per pair of SIMDs on a 256-CU part
-    const dim3 grid(blocks), wg(2 * BLOCK);
-    if (p.out32 != nullptr && sparse) {                  // compact outcome rows for a list of groups (rg_submit32c_sparse): row i of every column belongs to group gid[i]
-        if (p.force_wide != 0) {
-            if (many) hipLaunchKernelGGL((step32_wide_kernel<F, true, 4, true>), grid, wg, 0, s, p);
-            else      hipLaunchKernelGGL((step32_wide_kernel<F, true, 1, true>), grid, wg, 0, s, p);
-        } else {
-            if (many) hipLaunchKernelGGL((step32_kernel<F, true, 4, true>), grid, wg, 0, s, p);
-            else      hipLaunchKernelGGL((step32_kernel<F, true, 1, true>), grid, wg, 0, s, p);
-        }
-        return hipGetLastError();
-    }
-    if (p.out32 != nullptr) {                            // compact outcome rows (rg_submit32c)
-        if (p.force_wide != 0) {
-            if (many) hipLaunchKernelGGL((step32_wide_kernel<F, false, 4, true>), grid, wg, 0, s, p);
-            else      hipLaunchKernelGGL((step32_wide_kernel<F, false, 1, true>), grid, wg, 0, s, p);
-        } else {
-            if (many) hipLaunchKernelGGL((step32_kernel<F, false, 4, true>), grid, wg, 0, s, p);
-#ifdef RG_IOW2
-            else      hipLaunchKernelGGL((step32_kernel<F, false, 1, true, 2>), grid, dim3(3 * BLOCK), 0, s, p);
-#else
-            else      hipLaunchKernelGGL((step32_kernel<F, false, 1, true>), grid, wg, 0, s, p);
-#endif
-        }
-        return hipGetLastError();
-    }
-    if (p.force_wide != 0) {
-        if (sparse) {
-            if (many) hipLaunchKernelGGL((step32_wide_kernel<F, true, 4, false>), grid, wg, 0, s, p);
-            else      hipLaunchKernelGGL((step32_wide_kernel<F, true, 1, false>), grid, wg, 0, s, p);
-        } else {
-            if (many) hipLaunchKernelGGL((step32_wide_kernel<F, false, 4, false>), grid, wg, 0, s, p);
-            else      hipLaunchKernelGGL((step32_wide_kernel<F, false, 1, false>), grid, wg, 0, s, p);
-        }
-        return hipGetLastError();
-    }
-    if (sparse) {
-        if (many) hipLaunchKernelGGL((step32_kernel<F, true, 4, false>), grid, wg, 0, s, p);
-        else      hipLaunchKernelGGL((step32_kernel<F, true, 1, false>), grid, wg, 0, s, p);
-    } else {
-        if (many) hipLaunchKernelGGL((step32_kernel<F, false, 4, false>), grid, wg, 0, s, p);
-        else      hipLaunchKernelGGL((step32_kernel<F, false, 1, false>), grid, wg, 0, s, p);
-    }
-    return hipGetLastError();
-}
-
-// shape: 0 = step_split_kernel, 64 = step_kernel (wide rows); 32 = step32_kernel (compact rows: p.abcd32 set)
-template <int F>
-static hipError_t launch_f(const StepParams &p, bool sparse, int shape, hipStream_t s)
-{
-    switch (shape) {
-    case 0:  return launch_split<F>(p, sparse, s);
-    case 64: return launch_single<F>(p, sparse, s);
-    case 32: return launch_compact<F>(p, sparse, s);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-// clusters of 8 .. 15 nodes: the wide-row kernels (ABI 5) and, for a table with RG_OPT_COMPACT_ANY_CLUSTER, the compact-row kernels — the decision code is generic
-// in F (the quorum select is an insertion network, the follower records live in LDS, the class word carries a 4-bit follower index: rg_tier1n.hpp). ONE register
-// budget (WAVES = 1: whatever the allocator wants) whatever the size of the launch: with 7 .. 14 followers' matchIndex values in registers the allocator asks for
-// 120 .. 202 VGPRs, so a 128-VGPR variant could only be had by spilling from 9 followers on, and the LDS (25 .. 38 KB per workgroup) caps a CU at four to six
-// workgroups anyway.
-template <int F>
-static hipError_t launch_compact_big(const StepParams &p, bool sparse, hipStream_t s)
-{
-    const uint32_t blocks = (p.count + BLOCK - 1) / BLOCK;
-    if (blocks == 0) return hipSuccess;
-    if (p.count >= (1u << 28)) return hipErrorInvalidValue;       // the I/O wavefront addresses a row as scalar base + 32-bit lane offset
-    const dim3 grid(blocks), wg(2 * BLOCK);
-    const bool out32 = p.out32 != nullptr;
-    if (p.force_wide != 0) {
-        if (out32) { if (sparse) hipLaunchKernelGGL((step32_wide_kernel<F, true, 1, true>), grid, wg, 0, s, p); else hipLaunchKernelGGL((step32_wide_kernel<F, false, 1, true>), grid, wg, 0, s, p); }
-        else       { if (sparse) hipLaunchKernelGGL((step32_wide_kernel<F, true, 1, false>), grid, wg, 0, s, p); else hipLaunchKernelGGL((step32_wide_kernel<F, false, 1, false>), grid, wg, 0, s, p); }
-    } else {
-        if (out32) { if (sparse) hipLaunchKernelGGL((step32_kernel<F, true, 1, true>), grid, wg, 0, s, p); else hipLaunchKernelGGL((step32_kernel<F, false, 1, true>), grid, wg, 0, s, p); }
-        else       { if (sparse) hipLaunchKernelGGL((step32_kernel<F, true, 1, false>), grid, wg, 0, s, p); else hipLaunchKernelGGL((step32_kernel<F, false, 1, false>), grid, wg, 0, s, p); }
-    }
-    return hipGetLastError();
-}
-
-// Which of the follower counts 7 .. 14 a build has kernels for (bit F of the mask): all of them, or — an analysis build with RG_BUILD_ONLY_F4 — none, or the
-// ones -DRG_BUILD_ALSO_F=<mask> names (tests/test_compact_large_cluster_static_cpu.py: (1 << 8) | (1 << 14)).
+// ---- LAUNCHES BY FOLLOWER COUNT: one dispatcher for every kernel family that is a template on F ------------------------------------------------------------------
+// Which follower counts a build has kernels for (bit F of the mask, F = 1 .. 14): all of them, or — an analysis build with RG_BUILD_ONLY_F4 (tools/spine.sh: one
+// cluster size, seconds instead of a minute) — 4 alone, plus the ones -DRG_BUILD_ALSO_F=<mask> names (tests/test_compact_large_cluster_static_cpu.py:
+// (1 << 8) | (1 << 14)). A launch for a follower count the build lacks answers hipErrorInvalidValue, in every family.
 #if !defined(RG_BUILD_ONLY_F4)
-#define RG_BIG_F_MASK 0x7F80u
+#define RG_F_MASK 0x7FFEu
 #elif defined(RG_BUILD_ALSO_F)
-#define RG_BIG_F_MASK (RG_BUILD_ALSO_F)
+#define RG_F_MASK ((1u << 4) | (RG_BUILD_ALSO_F))
 #else
-#define RG_BIG_F_MASK 0u
+#define RG_F_MASK (1u << 4)
 #endif
-#define RG_BIG_F(F_) ((((RG_BIG_F_MASK) >> (F_)) & 1u) ? (F_) : 0)      // F_ where the build has it, else 0: launch_big<0> and its like answer hipErrorInvalidValue
 
-// TRANSLATION UNITS. The kernels of 7 .. 14 followers are half of this file's compile time, and a translation unit is compiled by one thread. Their
-// launchers are therefore function templates over a RANGE of four follower counts (LO = 7: 7 .. 10, LO = 11: 11 .. 14) that a build may instantiate in
-// translation units of their own: the Makefile compiles rg_kernels.hip three times — -DRG_TU=1: everything else, the ranges declared `extern template`;
-// -DRG_TU=7 and -DRG_TU=11: one range each and nothing that is not a template — side by side. Without RG_TU (the host emulation of tests/devemu, the analysis
-// builds) one translation unit holds everything, as before. A kernel is launched from the unit that holds it: no relocatable device code is needed.
+// TRANSLATION UNITS. The kernels of 7 .. 14 followers are half of this file's compile time, and a translation unit is compiled by one thread. They are therefore
+// launched from a function template over a RANGE of four follower counts (LO = 7: 7 .. 10, LO = 11: 11 .. 14) that a build may instantiate in translation units of
+// their own: the Makefile compiles rg_kernels.hip three times — -DRG_TU=1: everything else, the ranges declared `extern template`; -DRG_TU=7 and -DRG_TU=11: one
+// range each and nothing that is not a template — side by side. Without RG_TU (the host emulation of tests/devemu, the analysis builds) one translation unit holds
+// everything. A kernel is launched from the unit that holds it: no relocatable device code is needed.
+// A FAMILY is a launcher: a struct that holds the arguments of one launch and has `template <int F> hipError_t run() const`, which checks them and launches the
+// family's kernel for F followers. launch_followers(launcher, followers) is all a public launch_* entry point does; RG_FOLLOWER_LAUNCHERS (rg_kernels.hip) lists the
+// launchers whose ranges live in the range units, and the list makes both the `extern template` declarations and the instantiations.
+// (run() names its arguments through locals, not members: while a graph is recorded the host emulation's launch macro keeps what the launch expression names
+//  by copy, and of a member that would be `this` — a launcher is gone when the graph runs. It also wants the kernel's own name in the launch expression.)
 #if !defined(RG_TU) || RG_TU == 1
 #define RG_TU_MAIN 1                // this unit holds what is not a template: the kernels and launchers without a follower count, and the public launch_* entry points
 #endif
 
-template <int F>
-static hipError_t launch_big(const StepParams &p, bool sparse, int shape, hipStream_t s)
+template <class L, int F>
+static hipError_t launch_one(const L &l)
 {
-    if constexpr (F == 0) return hipErrorInvalidValue;
-    else switch (shape) {
-    case 0:  return launch_split<F>(p, sparse, s);
-    case 64: return launch_single<F>(p, sparse, s);
-    case 32: return launch_compact_big<F>(p, sparse, s);
-    default: return hipErrorInvalidValue;
-    }
+    if constexpr (((RG_F_MASK) >> F) & 1u) return l.template run<F>();
+    else return hipErrorInvalidValue;
 }
-template <int LO>
-hipError_t launch_step_range(const StepParams &p, int followers, bool sparse, int shape, hipStream_t s)
+template <class L, int LO>
+hipError_t launch_range(const L &l, int followers)
 {
     switch (followers - LO) {
-    case 0: return launch_big<RG_BIG_F(LO)>(p, sparse, shape, s);
-    case 1: return launch_big<RG_BIG_F(LO + 1)>(p, sparse, shape, s);
-    case 2: return launch_big<RG_BIG_F(LO + 2)>(p, sparse, shape, s);
-    case 3: return launch_big<RG_BIG_F(LO + 3)>(p, sparse, shape, s);
+    case 0: return launch_one<L, LO>(l);
+    case 1: return launch_one<L, LO + 1>(l);
+    case 2: return launch_one<L, LO + 2>(l);
+    case 3: return launch_one<L, LO + 3>(l);
     default: return hipErrorInvalidValue;
     }
 }
-#define RG_STEP_RANGE(LO_) hipError_t launch_step_range<LO_>(const StepParams &, int, bool, int, hipStream_t)
-#if defined(RG_TU) && RG_TU == 1
-extern template RG_STEP_RANGE(7); extern template RG_STEP_RANGE(11);
-#elif defined(RG_TU)
-template RG_STEP_RANGE(RG_TU);
-#endif
-#undef RG_STEP_RANGE
-
-#ifdef RG_TU_MAIN
-hipError_t launch_step(const StepParams &p, int followers, bool sparse, int shape, hipStream_t s)
+template <class L>
+static hipError_t launch_followers(const L &l, int followers)
 {
     switch (followers) {
-#ifndef RG_BUILD_ONLY_F4            // analysis builds (tools/spine.sh): one cluster size, seconds instead of a minute
-    case 1: return launch_f<1>(p, sparse, shape, s);
-    case 2: return launch_f<2>(p, sparse, shape, s);
-    case 3: return launch_f<3>(p, sparse, shape, s);
-    case 5: return launch_f<5>(p, sparse, shape, s);
-    case 6: return launch_f<6>(p, sparse, shape, s);
-#endif
-    case 4: return launch_f<4>(p, sparse, shape, s);
-    case 7: case 8: case 9: case 10: return launch_step_range<7>(p, followers, sparse, shape, s);
-    case 11: case 12: case 13: case 14: return launch_step_range<11>(p, followers, sparse, shape, s);
+    case 1: return launch_one<L, 1>(l);
+    case 2: return launch_one<L, 2>(l);
+    case 3: return launch_one<L, 3>(l);
+    case 4: return launch_one<L, 4>(l);
+    case 5: return launch_one<L, 5>(l);
+    case 6: return launch_one<L, 6>(l);
+    case 7: case 8: case 9: case 10: return launch_range<L, 7>(l, followers);
+    case 11: case 12: case 13: case 14: return launch_range<L, 11>(l, followers);
     default: return hipErrorInvalidValue;
     }
 }
+
+// a run-time bool as a template argument: fn(std::true_type) or fn(std::false_type)
+template <class Fn>
+static hipError_t lift(bool b, Fn fn) { return b ? fn(std::true_type{}) : fn(std::false_type{}); }
+
+// The register budget of the two-wavefront kernels (step32_kernel and its kin, the tick kernels) for a launch of MORE than one workgroup per pair of SIMDs on a
+// 256-CU part (1 024 workgroups); a smaller launch takes WAVES = 1. Up to 6 followers: WAVES = 4, the 128-VGPR variant (above). Clusters of 8 .. 15 nodes — the
+// wide-row kernels (ABI 5) and, for a table with RG_OPT_COMPACT_ANY_CLUSTER, the compact-row and tick kernels; the decision code is generic in F (the quorum select
+// is an insertion network, the follower records live in LDS, the class word carries a 4-bit follower index: rg_tier1n.hpp) — have ONE budget, WAVES = 1, whatever
+// the size of the launch: with 7 .. 14 followers' matchIndex values in registers the allocator asks for 120 .. 202 VGPRs, so a 128-VGPR variant could only be had
+// by spilling from 9 followers on, and the LDS (25 .. 38 KB per workgroup) caps a CU at four to six workgroups anyway.
+template <int F> constexpr int WAVES_MANY = F <= 6 ? 4 : 1;
+constexpr uint32_t MANY_BLOCKS = 1024u;
+#ifdef RG_IOW2                      // experiment build: two I/O wavefronts in the small dense launch with compact outcome rows
+constexpr int SMALL_IOW = 2;
+#else
+constexpr int SMALL_IOW = 1;
 #endif
+
+template <int F, bool SPARSE, bool OUT32>
+static hipError_t launch_compact(const StepParams &p, hipStream_t s)
+{
+    const uint32_t blocks = (p.count + BLOCK - 1) / BLOCK;
+    if (p.count >= (1u << 28)) return hipErrorInvalidValue;       // the I/O wavefront addresses a row as scalar base + 32-bit lane offset
+    // OUT32: compact outcome rows (rg_submit32c; SPARSE: rg_submit32c_sparse — row i of every column belongs to group gid[i])
+    constexpr int MANY = WAVES_MANY<F>, IOW = (F <= 6 && OUT32 && !SPARSE) ? SMALL_IOW : 1;
+    const bool many = blocks > MANY_BLOCKS;
+    const dim3 grid(blocks), wg(2 * BLOCK);
+    if (p.force_wide != 0) {
+        if (many) hipLaunchKernelGGL((step32_wide_kernel<F, SPARSE, MANY, OUT32>), grid, wg, 0, s, p);
+        else      hipLaunchKernelGGL((step32_wide_kernel<F, SPARSE, 1, OUT32>), grid, wg, 0, s, p);
+    } else {
+        if (many) hipLaunchKernelGGL((step32_kernel<F, SPARSE, MANY, OUT32>), grid, wg, 0, s, p);
+        else      hipLaunchKernelGGL((step32_kernel<F, SPARSE, 1, OUT32, IOW>), grid, dim3((1 + IOW) * BLOCK), 0, s, p);
+    }
+    return hipGetLastError();
+}
+
+// the step kernels. shape: 0 = step_split_kernel, 64 = step_kernel (wide rows); 32 = step32_kernel (compact rows: p.abcd32 set)
+struct StepLaunch {
+    const StepParams &p;
+    bool sparse;
+    int shape;
+    hipStream_t s;
+    template <int F> hipError_t run() const
+    {
+        if (shape != 0 && shape != 64 && shape != 32) return hipErrorInvalidValue;
+        const StepParams &p = this->p;
+        const hipStream_t s = this->s;
+        const dim3 grid((p.count + BLOCK - 1) / BLOCK);
+        if (grid.x == 0) return hipSuccess;
+        return lift(sparse, [&](auto sp) {
+            constexpr bool SPARSE = decltype(sp)::value;
+            if (shape == 32) return lift(p.out32 != nullptr, [&](auto o) { return launch_compact<F, SPARSE, decltype(o)::value>(p, s); });
+            if (shape == 64) hipLaunchKernelGGL((step_kernel<F, SPARSE>), grid, dim3(BLOCK), 0, s, p);
+            else             hipLaunchKernelGGL((step_split_kernel<F, SPARSE>), grid, dim3(2 * BLOCK), 0, s, p);
+            return hipGetLastError();
+        });
+    }
+};
 
 }  // namespace rg
