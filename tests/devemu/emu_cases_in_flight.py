@@ -19,6 +19,11 @@ def test_a_constructed_sequence_gives_the_literal_counts_and_kinds():
 
 
 @device
+def test_counts_at_the_end_of_a_uint16_neither_wrap_nor_stick():
+    I.saturation_case()
+
+
+@device
 @pytest.mark.parametrize("G,P,seed,resident", [(256, 5, 321, False), (200, 5, 77, True), (192, 3, 11, False), (192, 7, 16, True)])
 def test_the_tick_in_lockstep_with_the_oracle_and_the_model(G, P, seed, resident):
     """(small tables do not reach every line of MUST_SEE: tests/test_in_flight_cpu.py shows that for the sizes the MI355X runs)"""

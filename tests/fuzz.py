@@ -50,18 +50,28 @@ class View:
 
 
 class Fuzzer:
-    def __init__(self, groups, cluster, self_slot, seed, assert_rate=0.01, allow_miss=True):
+    def __init__(self, groups, cluster, self_slot, seed, assert_rate=0.01, allow_miss=True, far_stale=0.0, far_ack=0.0, far_vote=0.0):
         self.G, self.P, self.self_slot = groups, cluster, self_slot
         self.rng = random.Random(seed)
         self.others = [s for s in range(cluster) if s != self_slot]
         self.assert_rate = assert_rate
         self.allow_miss = allow_miss     # False: never draw an event whose lookups leave the cached term runs
+        # The "far" draws: small ABSOLUTE values that meet a state whose terms / epochs / indices were shifted to a chosen magnitude
+        # (random_initial_state's offsets). Off by default; each has its own probability and its own generator, so a stream drawn without them
+        # is the stream this class has always drawn, byte for byte (self.rng is never consulted for them).
+        self.far_stale, self.far_ack, self.far_vote = far_stale, far_ack, far_vote
+        self.rng_stale, self.rng_ack, self.rng_vote = (random.Random((seed << 2) ^ k) for k in (0xFA51, 0xFA52, 0xFA53))
+
+    def _far(self, rate, rng):
+        return rate > 0 and rng.random() < rate
 
     # -- building blocks -------------------------------------------------------------------------
     def _ae(self, b, r, g, v):
         rng = self.rng
         term = rng.choices([v.term - 1, v.term, v.term + 1, v.term + 3], [4, 80, 12, 4])[0]
         term = max(term, 0)
+        if self._far(self.far_stale, self.rng_stale):
+            term = self.rng_stale.choice([1, 2])             # a request from a leader of long ago
         leader = v.leader if (v.leader != abi.NO_NODE and rng.random() < 0.9) else rng.choice(self.others)
         if rng.random() < self.assert_rate:
             leader = rng.randrange(self.P)
@@ -123,6 +133,8 @@ class Fuzzer:
         rng = self.rng
         term = rng.choices([v.term - 1, v.term, v.term + 1, v.term + 2], [5, 20, 60, 15])[0]
         term = max(term, 0)
+        if self._far(self.far_stale, self.rng_stale):
+            term = self.rng_stale.choice([1, 2])             # a candidate of long ago
         cand = rng.choice(self.others) if rng.random() > self.assert_rate else rng.randrange(self.P)
         if v.has_log:
             li = v.last + rng.choice([-2, -1, 0, 0, 0, 1, 4])
@@ -130,6 +142,8 @@ class Fuzzer:
         else:
             li = v.eidx + rng.choice([-1, 0, 0, 1, 3])
             lt = v.eterm + rng.choice([0, 0, 0, 1]) - (1 if rng.random() < self.assert_rate else 0)
+        if self._far(self.far_vote, self.rng_vote):
+            li, lt = 1, 1                                    # a candidate whose log holds one entry of term 1
         b.put(r, g, abi.EV_PV_REQ if pre else abi.EV_RV_REQ, slot=cand, a=term, b=max(li, 0), c=max(lt, 0))
 
     def _ack(self, b, r, g, v):
@@ -140,6 +154,8 @@ class Fuzzer:
         resp = v.term if rng.random() < 0.97 else v.term + rng.randint(1, 2)
         epoch = v.epoch if rng.random() < 0.95 else max(v.epoch - 1, 0)
         at_send = rng.choices([v.eidx, le, max(le - 1, 0), v.eidx + 1], [70, 20, 5, 5])[0]
+        if self._far(self.far_ack, self.rng_ack):
+            epoch = 1                                        # the answer to a request the node's first participant sent
         if pend and rng.random() < 0.7:
             b.put(r, g, abi.EV_IS_ACK, slot=peer, flag=int(rng.random() < 0.8), a=resp, b=at_send, aux=epoch)
             return
@@ -258,9 +274,31 @@ class Fuzzer:
                     self._vote_reply(b, r, g, v, pre=False)
 
 
-def random_initial_state(groups, cluster, self_slot, seed, offset=0):
+def shift_state(st, term_offset=0, epoch_offset=0, groups=None):
+    """Move the terms and / or the role epochs of a state image (of `groups`, a slice or an index array; None: all) to another magnitude, consistently:
+    term_offset is added to currentTerm, to the term of every cached run, to a non-zero epoch.term and to a non-zero elected_term (a zero term stays 0: "none");
+    epoch_offset to role_epoch and to a non-zero elected_epoch. Differences between the moved values — all a decision depends on — stay as they were."""
+    sel = slice(None) if groups is None else groups
+    K = abi.TERM_RUNS
+    if term_offset:
+        st.current_term[sel] += term_offset
+        runs = st.run_term.reshape(-1, K)[sel]
+        live = np.arange(K)[None, :] < st.run_count[sel].astype(np.int64)[:, None]
+        st.run_term.reshape(-1, K)[sel] = np.where(live & (runs != 0), runs + term_offset, runs)
+        for name in ("epoch_term", "elected_term"):
+            col = getattr(st, name)[sel]
+            getattr(st, name)[sel] = np.where(col != 0, col + term_offset, col)
+    if epoch_offset:
+        st.role_epoch[sel] += np.uint32(epoch_offset)
+        col = st.elected_epoch[sel]
+        st.elected_epoch[sel] = np.where(col != 0, col + np.uint32(epoch_offset), col)
+    return st
+
+
+def random_initial_state(groups, cluster, self_slot, seed, offset=0, term_offset=0, epoch_offset=0):
     """Mixed-role start: followers/candidates/leaders with logs of 1-3 term runs, epochs, peers. offset > 0: long-lived groups — every log was
-    compacted at or above `offset` (epoch.index >= offset), so all their live indices are huge while their spans stay small."""
+    compacted at or above `offset` (epoch.index >= offset), so all their live indices are huge while their spans stay small. term_offset / epoch_offset:
+    the same image with its terms / role epochs moved up by that much (shift_state, applied after the last draw: the draws are those of offset alone)."""
     rng = random.Random(seed ^ 0x5EED)
     st = abi.GroupState(groups, cluster)
     Fn = cluster - 1
@@ -298,7 +336,7 @@ def random_initial_state(groups, cluster, self_slot, seed, offset=0):
                 st.peer_last_epoch[g * Fn + j] = eidx
                 st.peer_match_index[g * Fn + j] = m
                 st.peer_next_index[g * Fn + j] = (m + 1) if m else top + 1
-    return st
+    return shift_state(st, term_offset, epoch_offset)
 
 
 def concat_batches(batches):

@@ -321,6 +321,65 @@ def constructed_case(G=96):
     orc.close()
 
 
+def saturation_case(G=96):
+    """The counts at the end of a uint16: rg_in_flight_set gives follower A 0xFFFE and follower B 0xFFFF in flight, then a command and a heartbeat trigger the send
+    step. Both followers are far beyond either limit, so every send is RG_SEND_GATED and nothing is counted up: the counts stand (no wrap to 0 — the model saturates
+    at 0xFFFF, the kernel clamps where it adds); an ack takes exactly one off the follower it names, 0xFFFF included; the neighbour's counts never move."""
+    L, N, A_, B_ = 5, 6, 1, 2
+    TOP = 0xFFFF
+    st0 = make_state(3, G)
+    set_group(st0, L, role=abi.LEADER, term=3, voted_for=0, role_epoch=7, commit=5, log=simple_log(10, term=3))
+    gpu, orc = engine.Table(G, 3, 0, False), oracle_lib.OracleTable(G, 3, 0, False)
+    gpu.set_device_in_flight(True)
+    for x in (gpu, orc):
+        x.load_state(st0)
+        x.timers_configure(900, 300, 1)
+        x.timers_arm(1000)
+    model = Model(G, 3, 0)
+    model.counts[L] = (TOP - 1, TOP)
+    model.counts[N] = (TOP, TOP - 1)
+    gpu.in_flight_set(model.counts)
+    assert np.array_equal(gpu.in_flight_read(), model.counts)
+    tick = engine.Tick2(gpu, 1, entry_cap=64, expired_cap=G, critical_point=1, cool_down_ms=60, sparse_cap=G)
+    gid = np.array([L], dtype=np.uint32)
+    clock = [1000]
+
+    def step(kind, counts, kinds, reserved, **kw):
+        clock[0] += 10
+        now = [clock[0]]
+        b = abi.Batch(1, 1, gid=gid)
+        b.put(0, 0, kind, **kw)
+        oo = orc.submit(b, now=now)
+        orc.timers_update(1, 1, oo.reply, now, gid=gid)
+        assert abi.flags_status(int(oo.reply["flags"][0])) == abi.OK, (kind, abi.flags_status(int(oo.reply["flags"][0])))
+        command, heartbeat = model.walk(gid, b.head["hdr"].reshape(1, 1), oo.reply["flags"].reshape(1, 1))
+        want = model.plan(orc, gid, command, heartbeat)
+        tick.refill(b, now)
+        tick.launch()
+        tick.wait()
+        where = "step at %d (kind %d)" % (clock[0], kind)
+        got = tick.sends()
+        same_sends(got, want, np.ones(1, dtype=bool), where)
+        orc.timers_expired_epochs(clock[0], capacity=G)
+        have = gpu.in_flight_read()
+        assert np.array_equal(have, model.counts), where
+        assert tuple(have[L]) == counts and tuple(got[1]["kind"][0]) == kinds and int(got[0]["reserved"][0]) == reserved, (where, have[L], got[1]["kind"][0], got[0]["reserved"][0])
+        assert tuple(have[N]) == (TOP, TOP - 1), where
+        compare_states(orc.read_state(), gpu.read_state(), where)
+
+    GATED, NONE = (abi.SEND_GATED,) * 2, (abi.SEND_NONE,) * 2
+    HB, CMD = abi.SENT_TRIGGERED | abi.SENT_HEARTBEAT, abi.SENT_TRIGGERED
+    step(abi.EV_CLIENT_APPEND, (TOP - 1, TOP), GATED, CMD, n=1)          # acceptCommand: the limit is 20
+    step(abi.EV_TIMEOUT, (TOP - 1, TOP), GATED, HB)                     # onTimeout: the limit is 2
+    step(abi.EV_AE_ACK, (TOP - 1, TOP - 1), NONE, 0, slot=B_, flag=1, a=3, b=0, c=10, aux=7)      # one down from the top
+    step(abi.EV_AE_ACK, (TOP - 2, TOP - 1), NONE, 0, slot=A_, flag=1, a=3, b=0, c=10, aux=7)
+    step(abi.EV_CLIENT_APPEND, (TOP - 2, TOP - 1), GATED, CMD, n=1)
+    assert model.seen["gated_command"] >= 4 and model.seen["decrement"] == 2
+    tick.close()
+    gpu.close()
+    orc.close()
+
+
 # ---- 3. the forms agree -------------------------------------------------------------------------------------------------------------------------------------------
 def _pair(G, P, seed):
     a, d, fz, rng = X._pair(G, P, seed)

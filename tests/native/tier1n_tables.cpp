@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstdint>
+#include <string>
 #include <vector>
 #include "hip/hip_runtime.h"
 #include "../../rafting_amd/csrc/rg_step.hpp"
@@ -112,8 +113,35 @@ static void class_word_table()
     std::printf("class word: %ld rows checked\n", rows);
 }
 
-int main()
+// `dump`: the primitives' answers on operands read from the command line's table below, one line each, for tests/test_kernel_static_cpu.py to hold against exact
+// Python integers: "lt x y t", "ne x y t", "pos x t" (t: the sign bit of the word), "rel x base r", "abs r base x"
+static int dump()
 {
+    const int64_t H = 1ll << 29, L = 1ll << 30, M = 1ll << 31;
+    const int64_t in[] = {0, 1, 2, H - 1, H + 1, L - 1, L, L + H - 1};                      // the domain: every value below 2^30 + 2^29
+    const int64_t out[] = {-1, 5, -L - 1, -L, L, L + H, -M, M - 1};                          // around it: the documented failure points are among these pairs
+    for (int pass = 0; pass < 2; pass++) {
+        const int64_t *v = pass ? out : in;
+        for (int i = 0; i < 8; i++) {
+            for (int j = 0; j < 8; j++) {
+                std::printf("lt %lld %lld %d\n", (long long)v[i], (long long)v[j], (int)(s_lt((int32_t)v[i], (int32_t)v[j]) < 0));
+                std::printf("ne %lld %lld %d\n", (long long)v[i], (long long)v[j], (int)(s_ne((int32_t)v[i], (int32_t)v[j]) < 0));
+            }
+            std::printf("pos %lld %d\n", (long long)v[i], (int)(s_pos((int32_t)v[i]) < 0));
+        }
+    }
+    for (int64_t base : {(int64_t)0, (int64_t)1 << 40})
+        for (int64_t x : {(int64_t)0, base, base + 1, base + L - 1, base + M - 1}) {
+            const int64_t r = to_rel(x, base);
+            std::printf("rel %lld %lld %lld\n", (long long)x, (long long)base, (long long)r);
+            std::printf("abs %lld %lld %lld\n", (long long)r, (long long)base, (long long)to_abs(r, base));
+        }
+    return 0;
+}
+
+int main(int argc, char **argv)
+{
+    if (argc > 1 && std::string(argv[1]) == "dump") return dump();
     sign_words();
     predicate_word();
     class_word_table();

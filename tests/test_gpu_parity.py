@@ -1044,14 +1044,39 @@ def tick_path_case(G=192, P=5, ticks=24, seed=123):
     orc.close()
 
 
-def tick2_case(G=4096, P=5, ticks=40, seed=321, device_resident=False, nodes=None):
+def unpackable_rows(b, base):
+    """rows of the one-round dense batch b that the compact row format cannot hold relative to the groups' index bases `base`: a non-zero log index at or below
+    its group's base, or 2^31 and more above it; any other field outside [0, 2^31) (include/raftgpu.h, "the index base of the compact formats")"""
+    kind = b.head["hdr"] & 0xF
+    ixf = np.array([0, 0xA, 0x6, 0x2, 0x2, 0x2, 0, 0, 0, 0, 0x1, 0x2, 0, 0, 0, 0], dtype=np.uint32)[kind]
+    bad = np.zeros(b.count, dtype=bool)
+    for k, col in enumerate((b.ab["x"], b.ab["y"], b.cd["x"], b.cd["y"])):
+        is_ix = ((ixf >> k) & 1) != 0
+        bad |= is_ix & (col != 0) & ((col <= base) | (col - base >= (1 << 31)))
+        bad |= ~is_ix & ((col < 0) | (col >= (1 << 31)))
+    return bad
+
+
+def blank_rows(b, mask):
+    """RG_EV_NONE, every field 0, in the rows `mask` of batch b"""
+    b.head[mask], b.ab[mask], b.cd[mask] = (0, 0), (0, 0), (0, 0)
+
+
+def tick2_case(G=4096, P=5, ticks=40, seed=321, device_resident=False, nodes=None, make_state=None, fuzz_kw=None, index_base=None, watch=None, report=None):
     """The device-resident tick (rg_tick2_*, ABI 5): step32c -> timers_update32 -> health_update32 -> timers_expired -> replicate -> ready as ONE HIP graph,
     driven by its own timers: the tickets that fire become the TIMEOUT rows (with their role epochs) of the NEXT tick, tick after tick. Every tick is held
-    against the oracle doing the same with separate calls: outcome rows, deadlines, expired lists + epochs, health statistics, send table, readiness."""
+    against the oracle doing the same with separate calls: outcome rows, deadlines, expired lists + epochs, health statistics, send table, readiness.
+    make_state(G, P, self_slot, seed): the initial state instead of fuzz.random_initial_state's; fuzz_kw: further arguments of fuzz.Fuzzer (both: the
+    magnitudes of tests/domain_edge_cases.py); index_base: a function
+    of the initial state that gives the table's index bases — the rows then travel relative to them, and a row the format cannot hold that way is blanked;
+    watch(state, batch): called before every launch; report: a dict that receives the number of workgroups the 64-bit body decided."""
     self_slot = 2 % P
-    st0 = fuzz.random_initial_state(G, P, self_slot, seed)
+    st0 = (make_state or fuzz.random_initial_state)(G, P, self_slot, seed)
     gpu, orc = engine.Table(G, P, self_slot, True), oracle_lib.OracleTable(G, P, self_slot, True)
-    fz = fuzz.Fuzzer(G, P, self_slot, seed, allow_miss=False)
+    fz = fuzz.Fuzzer(G, P, self_slot, seed, allow_miss=False, **(fuzz_kw or {}))
+    base = None if index_base is None else index_base(st0)
+    if base is not None:
+        gpu.set_index_base(base)
     for t in (gpu, orc):
         t.load_state(st0)
         t.timers_configure(900, 300, 4321)
@@ -1079,13 +1104,18 @@ def tick2_case(G=4096, P=5, ticks=40, seed=321, device_resident=False, nodes=Non
         fz.round(cur, b, 0)
         for g, e in zip(fired_g, fired_e):                  # the tickets that fired at the end of the previous tick: their onTimeout, fenced
             b.head[int(g)] = (int(abi.hdr_make(abi.EV_TIMEOUT)), int(e))
-        assert abi.batch_fits_32(b)
+        if base is not None:
+            blank_rows(b, unpackable_rows(b, base))
+        else:
+            assert abi.batch_fits_32(b)
+        if watch is not None:
+            watch(cur, b)
         hb = (rng.random(G) < 0.5).astype(np.uint8)
         fl = rng.integers(0, 24, (G, P - 1)).astype(np.uint16)
-        tick.refill(b, [now], heartbeat=hb, in_flight=fl.T.reshape(-1))
+        tick.refill(b, [now], heartbeat=hb, in_flight=fl.T.reshape(-1), index_base=base)
         tick.launch()
         tick.wait()
-        got, _ = engine.unpack32(tick.outcome32(), 1, G, cur.role_epoch)
+        got, _ = engine.unpack32(tick.outcome32(), 1, G, cur.role_epoch, index_base=base)
         # (an ack whose quorum index lies below the cached term runs: the host half of the NEED_HOST protocol, then the repaired rows folded like the others;
         #  what the graph derived for THOSE groups in this tick — send rows, readiness — was derived before the repair and is not compared)
         bad = np.flatnonzero(got.status == abi.NEED_HOST)
@@ -1118,12 +1148,16 @@ def tick2_case(G=4096, P=5, ticks=40, seed=321, device_resident=False, nodes=Non
         seen_fired += len(eg)
         seen_send += int(np.count_nonzero(so["kind"] == abi.SEND_APPEND))
     assert seen_fired > 0 and seen_send > 0
+    if report is not None:
+        report["wide_bodies"], report["repaired"] = gpu.wide_body_workgroups(), repaired
     # the separate calls on compact rows give what the wide ones give: one more batch, through rg_submit32c + rg_timers_update32 / rg_health_update32
     b = abi.Batch(1, G)
     cur = gpu.read_state()
     fz.round(cur, b, 0)
-    raw = gpu.submit32c(b)
-    got, _ = engine.unpack32(raw, 1, G, cur.role_epoch)
+    if base is not None:
+        blank_rows(b, unpackable_rows(b, base))
+    raw = gpu.submit32c(engine.pack32(b, index_base=base))
+    got, _ = engine.unpack32(raw, 1, G, cur.role_epoch, index_base=base)
     if not np.any(got.status == abi.NEED_HOST):
         oo = orc.submit(b, now=[99_000])
         gpu.timers_update32(1, raw, [99_000])

@@ -18,6 +18,10 @@ def test_a_constructed_sequence_gives_the_literal_counts_and_kinds():
     I.constructed_case()
 
 
+def test_counts_at_the_end_of_a_uint16_neither_wrap_nor_stick():
+    I.saturation_case()
+
+
 @pytest.mark.parametrize("resident", [False, True], ids=["host-pinned", "device-resident"])
 @pytest.mark.parametrize("G,P,seed,ticks,first", SIZES)
 def test_the_tick_in_lockstep_with_the_oracle_and_the_model(G, P, seed, ticks, first, resident):

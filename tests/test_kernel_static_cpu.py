@@ -89,3 +89,56 @@ def test_sign_word_primitives_and_the_io_wavefronts_tables(tmp_path):
                    check=True, timeout=600)
     p = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert p.returncode == 0 and "tier1n tables ok" in p.stdout, p.stdout[-3000:]
+
+
+def test_sign_words_and_relative_indices_against_python_integers(tmp_path):
+    """The same program's `dump`: s_lt / s_ne / s_pos on every pair from {0, 1, 2, 2^29 -+ 1, 2^30 - 1, 2^30, 2^30 + 2^29 - 1} — the domain rg_tier1n.hpp states —
+    against Python's exact integers, and on operands just outside it, where the header's domain statement is itself pinned: the answer is right while
+    |x - y| < 2^31 (s_lt; -2^31 itself still reads right), x ^ y <= 2^31 (s_ne) and x > -2^31 (s_pos), and is the documented WRONG one beyond. Then to_rel /
+    to_abs (rg_device.hpp) at base 0 and 2^40: 0 is "none" both ways, x == base != 0 has no image (-1, which fails every range check), anything else round-trips."""
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    exe = str(tmp_path / "tier1n_tables")
+    subprocess.run(["g++", "-O1", "-std=c++17", "-w", "-I" + os.path.join(ROOT, "tests", "devemu"), "-I" + os.path.join(ROOT, "include"),
+                    os.path.join(ROOT, "tests", "native", "tier1n_tables.cpp"), os.path.join(ROOT, "tests", "devemu", "emu_runtime.cpp"), "-pthread", "-o", exe],
+                   check=True, timeout=600)
+    p = subprocess.run([exe, "dump"], capture_output=True, text=True, timeout=60)
+    assert p.returncode == 0, p.stdout[-2000:]
+    H, L, M = 1 << 29, 1 << 30, 1 << 31
+    domain = {0, 1, 2, H - 1, H + 1, L - 1, L, L + H - 1}
+    i32 = lambda v: (v + M) % (2 * M) - M                                           # noqa: E731
+    seen = dict(lt=0, ne=0, pos=0, rel=0, abs=0, lt_wrong=0, ne_wrong=0, pos_wrong=0, in_domain=0)
+    rel = {}
+    for ln in p.stdout.splitlines():
+        op, *v = ln.split()
+        v = [int(x) for x in v]
+        seen[op] += 1
+        if op == "lt":
+            x, y, t = v
+            right = abs(x - y) < M or x - y == -M
+            assert (t == int(x < y)) == right, ln
+            assert right or t == int(i32(x - y) < 0), ln
+            seen["lt_wrong"] += not right
+            seen["in_domain"] += x in domain and y in domain and right
+        elif op == "ne":
+            x, y, t = v
+            u = (x ^ y) & (2 * M - 1)
+            right = u <= M
+            assert (t == int(x != y)) == right, ln
+            assert right or t == 0, ln                                              # (operands that differ in bit 31, and elsewhere, read as EQUAL)
+            assert not (x in domain and y in domain) or right, ln
+            seen["ne_wrong"] += not right
+        elif op == "pos":
+            x, t = v
+            assert (t == int(x > 0)) == (x > -M), ln
+            seen["pos_wrong"] += x == -M
+        elif op == "rel":
+            x, base, r = v
+            assert r == (0 if x == 0 else (-1 if x == base else x - base)), ln
+            rel[(r, base)] = x
+        else:
+            r, base, x = v
+            assert x == (0 if r == 0 else r + base), ln
+            assert x == rel[(r, base)] or (r == -1 and rel[(r, base)] == base != 0), ln      # the round trip; the one value without an image comes back as base - 1
+    assert seen["lt"] == seen["ne"] == 128 and seen["pos"] == 16 and seen["rel"] == seen["abs"] == 10, seen
+    assert seen["in_domain"] >= 64 and seen["lt_wrong"] > 0 and seen["ne_wrong"] > 0 and seen["pos_wrong"] == 1, seen
