@@ -558,7 +558,12 @@ int rg_replicate(rg_table_t *t, uint32_t count, const uint32_t *gid, const uint8
  *                     replaced by a new participant (TimerTicket.TIMEOUT makes resetTimer return false).
  *   rg_timers_expired lists, in ascending group order, every group whose deadline has passed (wavefront ballot +
  *                     popcount compaction) and marks its ticket fired: the host turns each into one RG_EV_TIMEOUT row.
- * now / deadlines are milliseconds on any monotonic clock of the host's choosing; deadline 0 = no ticket yet. */
+ * now / deadlines are milliseconds on a clock of the host's choosing (System.currentTimeMillis() in the reference), 64 bits wide throughout. THE CLOCK'S
+ * DOMAIN: 1 <= now <= 2^62 for every `now` of this header (rg_timers_*, rg_health_*, rg_ready, the clocks of a tick), and election_ms, heartbeat_ms >= 1.
+ * 0, negative values and INT64_MAX are marks of the deadline column — 0 = no ticket yet, -1 = the ticket fired, INT64_MAX = muted — so no clock and no
+ * deadline may coincide with them, and now + 2 * election_ms and now + heartbeat_ms must not wrap. A clock outside the domain is the host's error and is not
+ * refused, like an index outside [1, 2^30) relative to its base. The clock need not be monotonic: requestSuccess / requestFailure keep their maxima
+ * (increaseMono), and a deadline is whatever the last reset made it. */
 int rg_timers_configure(rg_table_t *t, int64_t election_ms, int64_t heartbeat_ms, uint64_t seed);
 /* reply: the rg_reply_t rows of the batch just submitted ([rounds*count], same gid convention as rg_submit);
  * now: [rounds] timestamp of every round. memspace applies to reply and gid (now is always a host array). */

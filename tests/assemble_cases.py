@@ -17,6 +17,7 @@ import numpy as np
 
 from rafting_amd import abi, engine
 from tests import auto_base_stream as S
+from tests.clock import origin as clock_origin
 from tests import fuzz, oracle_lib
 from tests import sparse_rounds_cases as X
 from tests.helpers import compare_outcomes, compare_states
@@ -384,7 +385,7 @@ def standalone_case(G, P, seed, launches):
     for t in (a, d, orc):
         t.load_state(st0)
     orc.timers_configure(900, 300, 4321)
-    orc.timers_arm(10_000)
+    orc.timers_arm(clock_origin())
     fz, rng = fuzz.Fuzzer(G, P, self_slot, seed, allow_miss=False), np.random.default_rng(seed)
     asm = engine.Assembler(a, X.RMAX * G, max_expired=G)
     fired_g, fired_e = np.zeros(0, np.uint32), np.zeros(0, np.uint32)

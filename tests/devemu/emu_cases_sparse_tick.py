@@ -14,6 +14,7 @@ WAVES = os.environ.get("RG_EMU_WAVES") == "1" and os.environ.get("RG_SPLIT") == 
 
 from rafting_amd import abi, engine  # noqa: E402
 from tests import fuzz, oracle_lib  # noqa: E402
+from tests import clock  # noqa: E402
 from tests import sparse_tick_cases as X  # noqa: E402
 from tests.helpers import compare_outcomes  # noqa: E402
 
@@ -71,12 +72,12 @@ def test_a_count_above_the_capacity_is_clamped():
     for t in (gpu, orc):
         t.load_state(st0)
         t.timers_configure(900, 300, 1)
-        t.timers_arm(10_000)
+        t.timers_arm(clock.origin())
     b = abi.Batch(1, G)
     fuzz.Fuzzer(G, P, 2, 44, allow_miss=False).round(gpu.read_state(), b, 0)
     rows = np.arange(0, given, dtype=np.int64)
     b32 = engine.pack32(X.subset(b, rows))
-    gid, count, now = rows.astype(np.uint32), np.array([given], np.uint32), np.array([10_100], np.int64)
+    gid, count, now = rows.astype(np.uint32), np.array([given], np.uint32), np.array([clock.origin() + 100], np.int64)
 
     def filled(dtype, n):
         a = np.zeros(n, dtype=dtype)
@@ -105,7 +106,7 @@ def test_a_count_above_the_capacity_is_clamped():
     out.persist[(out.row["flags"] & abi.F_PERSIST) == 0] = 0
     got, _ = engine.unpack32(out, 1, cap, st0.role_epoch[:cap])
     first = X.subset(b, rows[:cap])
-    oo = orc.submit(first, now=[10_100])
+    oo = orc.submit(first, now=[clock.origin() + 100])
     if not np.any(got.status == abi.NEED_HOST):
         compare_outcomes(oo, got, "the first `capacity` rows")
         ho, so = orc.replicate(gid=gid[:cap])

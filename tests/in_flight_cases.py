@@ -16,6 +16,7 @@ import pytest
 
 from rafting_amd import abi, engine
 from tests import assemble_cases as A
+from tests.clock import origin as clock_origin
 from tests import oracle_lib
 from tests import sparse_rounds_cases as X
 from tests.helpers import compare_states, make_state, set_group, simple_log
@@ -239,7 +240,7 @@ def constructed_case(G=96):
     gpu.in_flight_set(model.counts)
     tick = engine.Tick2(gpu, 1, entry_cap=64, expired_cap=G, critical_point=1, cool_down_ms=60, sparse_cap=G)
     gid = np.array([L], dtype=np.uint32)
-    clock = [1000]
+    clock = [clock_origin() - 9000]
 
     def step(kind, counts, kinds, reserved, status=None, role=None, **kw):
         clock[0] += 10
@@ -342,7 +343,7 @@ def saturation_case(G=96):
     assert np.array_equal(gpu.in_flight_read(), model.counts)
     tick = engine.Tick2(gpu, 1, entry_cap=64, expired_cap=G, critical_point=1, cool_down_ms=60, sparse_cap=G)
     gid = np.array([L], dtype=np.uint32)
-    clock = [1000]
+    clock = [clock_origin() - 9000]
 
     def step(kind, counts, kinds, reserved, **kw):
         clock[0] += 10
@@ -408,7 +409,7 @@ def same_as_dense_case(G, R=4, ticks=8, seed=9, P=5, device_resident=False):
             c = rng.integers(0, 24, (G, P - 1))
             a.in_flight_set(c)
             d.in_flight_set(c)
-        nows = [10_000 + 150 * k + 10 * r for r in range(R)]
+        nows = [clock_origin() + 150 * k + 10 * r for r in range(R)]
         cur = a.read_state()
         b = abi.Batch(R, G)
         for r in range(R):
@@ -458,7 +459,7 @@ def one_round_case(G, ticks=8, seed=9, P=5, device_resident=False):
         sub = subset(b, np.flatnonzero(pick))
         c0 = a.in_flight_read()
         for t in (ta, td):
-            t.refill(sub, [10_000 + 150 * k])
+            t.refill(sub, [clock_origin() + 150 * k])
             t.launch()
             t.wait()
         ed = _same(ta, td, a, d, "tick %d" % k)
@@ -610,7 +611,7 @@ def option_off_case(G=1000, P=5, seed=77, ticks=10, device_resident=False):
     assert ta.heartbeat is not None and ta.in_flight is not None
     fired_g, fired_e = np.zeros(0, np.uint32), np.zeros(0, np.uint32)
     for k in range(ticks):
-        nows = [10_000 + 150 * k + 10 * r for r in range(R)]
+        nows = [clock_origin() + 150 * k + 10 * r for r in range(R)]
         cur = a.read_state()
         b = abi.Batch(R, G)
         for r in range(R):

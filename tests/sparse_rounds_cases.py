@@ -23,6 +23,7 @@ import pytest
 
 from rafting_amd import abi, engine
 from tests import auto_base_stream as S
+from tests import clock
 from tests import fuzz, oracle_lib
 from tests.helpers import check_out32_rows, compare_outcomes, compare_states
 from tests.sparse_tick_cases import assert_untouched, repair_need_host, subset
@@ -34,7 +35,7 @@ KEEP = 0.6                                                   # share of the list
 
 
 def now_of(k, r):
-    return 10_000 + 150 * k + 10 * r
+    return clock.origin() + 150 * k + 10 * r
 
 
 def lead(orc, fz, rng, G, k, fired_g, fired_e, fold=True):
@@ -95,7 +96,7 @@ def _tables(G, P, seed, device=True):
         if t is not None:
             t.load_state(st0)
             t.timers_configure(900, 300, 4321)
-            t.timers_arm(10_000)
+            t.timers_arm(clock.origin())
     return gpu, orc, shadow, fuzz.Fuzzer(G, P, self_slot, seed, allow_miss=False), np.random.default_rng(seed), np.random.default_rng(seed + 1000)
 
 
@@ -385,7 +386,7 @@ def _pair(G, P, seed):
     for t in (a, d):
         t.load_state(st0)
         t.timers_configure(900, 300, 99)
-        t.timers_arm(10_000)
+        t.timers_arm(clock.origin())
     return a, d, fuzz.Fuzzer(G, P, self_slot, seed, allow_miss=False), np.random.default_rng(seed)
 
 
@@ -397,7 +398,7 @@ def one_round_case(G, ticks=12, seed=9, P=5, device_resident=False):
     ta, td = engine.Tick2(a, 1, sparse_rounds=True, **kw), engine.Tick2(d, 1, **kw)
     fired_g, fired_e = np.zeros(0, np.uint32), np.zeros(0, np.uint32)
     for k in range(ticks):
-        now = 10_000 + 150 * k
+        now = clock.origin() + 150 * k
         b = abi.Batch(1, G)
         fz.round(a.read_state(), b, 0)
         pick = rng.random(G) < (0.5, 0.05, 1.0)[k % 3]
@@ -436,7 +437,7 @@ def same_as_dense_case(G, R=4, ticks=10, seed=9, P=5, device_resident=False, dep
     fired_g, fired_e = np.zeros(0, np.uint32), np.zeros(0, np.uint32)
     every = np.arange(G, dtype=np.uint32)
     for k in range(ticks):
-        nows = [10_000 + 150 * k + 10 * r for r in range(R)]
+        nows = [clock.origin() + 150 * k + 10 * r for r in range(R)]
         cur = a.read_state()
         b = abi.Batch(R, G)
         for r in range(R):

@@ -9,6 +9,7 @@ import pytest
 
 from rafting_amd import abi, engine
 from tests import auto_base_stream as S
+from tests import clock
 from tests import fuzz, oracle_lib
 from tests import test_gpu_parity as T
 from tests.helpers import check_out32_rows, compare_outcomes, compare_states
@@ -100,14 +101,14 @@ def sparse_tick_case(G, seed, ticks, P=5, device_resident=False, capacity=None, 
     for t in (gpu, orc):
         t.load_state(st0)
         t.timers_configure(900, 300, 4321)
-        t.timers_arm(10_000)
+        t.timers_arm(clock.origin())
     tick = engine.Tick2(gpu, 1, entry_cap=8 * G, expired_cap=G, critical_point=1, cool_down_ms=60, device_resident=device_resident, sparse_cap=cap)
     fired_g, fired_e = np.zeros(0, np.uint32), np.zeros(0, np.uint32)
     rng = np.random.default_rng(seed)
     seen = dict(empty_with_fired=0, full=0, ragged=0, conversion=0, append=0, ready0=0, ready1=0)
     all_rows = left_out = 0
     for k in range(ticks):
-        now = 10_000 + 150 * k
+        now = clock.origin() + 150 * k
         fill = FILLS[k % len(FILLS)]
         cur = gpu.read_state()
         b = abi.Batch(1, G)
@@ -191,14 +192,14 @@ def same_as_dense_case(G, ticks=20, seed=9, P=5, device_resident=False):
     for t in (a, d):
         t.load_state(st0)
         t.timers_configure(900, 300, 99)
-        t.timers_arm(10_000)
+        t.timers_arm(clock.origin())
     kw = dict(entry_cap=8 * G, expired_cap=G, critical_point=1, cool_down_ms=60, device_resident=device_resident)
     ta, td = engine.Tick2(a, 1, sparse_cap=G, **kw), engine.Tick2(d, 1, **kw)
     rng = np.random.default_rng(seed)
     fired_g, fired_e = np.zeros(0, np.uint32), np.zeros(0, np.uint32)
     every = np.arange(G)
     for k in range(ticks):
-        now = 10_000 + 150 * k
+        now = clock.origin() + 150 * k
         b = abi.Batch(1, G)
         fz.round(a.read_state(), b, 0)
         for g, e in zip(fired_g, fired_e):

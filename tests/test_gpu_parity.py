@@ -10,6 +10,7 @@ import pytest
 
 from rafting_amd import abi, engine
 from tests import fuzz, kat_scenarios, oracle_lib
+from tests import clock
 from tests.helpers import set_group, compare_outcomes, compare_states, make_state, simple_log, check_out32_rows
 
 pytestmark = pytest.mark.gpu
@@ -412,11 +413,11 @@ def test_timer_driven_replay_matches_oracle():
     for t in (gpu, orc):
         t.load_state(st0)
         t.timers_configure(900, 300, 1234)
-        t.timers_arm(10_000)
+        t.timers_arm(clock.origin())
     assert np.array_equal(gpu.timers_read(), orc.timers_read())
     fired = 0
     for r in range(60):
-        now = 10_000 + 150 * r
+        now = clock.origin() + 150 * r
         eg, ng = gpu.timers_expired(now, capacity=G if r % 7 else 97)     # a short buffer now and then
         eo, no = orc.timers_expired(now, capacity=G if r % 7 else 97)
         assert ng == no and np.array_equal(eg, eo) and np.all(np.diff(eg.astype(np.int64)) > 0)
@@ -441,7 +442,7 @@ def test_timer_driven_replay_matches_oracle():
         big.put(k, 900, abi.EV_TIMEOUT)
     og, oo = gpu.submit(big), orc.submit(big)
     compare_outcomes(oo, og, "multi-round")
-    nows = [30_000, 30_100, 30_250]
+    nows = [clock.origin() + 20_000, clock.origin() + 20_100, clock.origin() + 20_250]
     gpu.timers_update(3, G, og.reply, nows)
     orc.timers_update(3, G, oo.reply, nows)
     assert np.array_equal(gpu.timers_read(), orc.timers_read())
@@ -1080,7 +1081,7 @@ def tick2_case(G=4096, P=5, ticks=40, seed=321, device_resident=False, nodes=Non
     for t in (gpu, orc):
         t.load_state(st0)
         t.timers_configure(900, 300, 4321)
-        t.timers_arm(10_000)
+        t.timers_arm(clock.origin())
     assert np.array_equal(gpu.timers_read(), orc.timers_read())
     # (nodes: how the tick is RECORDED — 1 = one kernel (the default), 2 = step + fused tail, 4 = step, fold, replicate, ready; read at rg_tick2_create)
     saved = os.environ.get("RG_TICK_NODES")
@@ -1098,7 +1099,7 @@ def tick2_case(G=4096, P=5, ticks=40, seed=321, device_resident=False, nodes=Non
     seen_fired = seen_send = repaired = 0
     rng = np.random.default_rng(seed)
     for k in range(ticks):
-        now = 10_000 + 150 * k
+        now = clock.origin() + 150 * k
         b = abi.Batch(1, G)
         cur = gpu.read_state()
         fz.round(cur, b, 0)
@@ -1159,10 +1160,10 @@ def tick2_case(G=4096, P=5, ticks=40, seed=321, device_resident=False, nodes=Non
     raw = gpu.submit32c(engine.pack32(b, index_base=base))
     got, _ = engine.unpack32(raw, 1, G, cur.role_epoch, index_base=base)
     if not np.any(got.status == abi.NEED_HOST):
-        oo = orc.submit(b, now=[99_000])
-        gpu.timers_update32(1, raw, [99_000])
-        gpu.health_update32(b, raw, [99_000])
-        orc.timers_update(1, G, oo.reply, [99_000])
+        oo = orc.submit(b, now=[clock.origin() + 89_000])
+        gpu.timers_update32(1, raw, [clock.origin() + 89_000])
+        gpu.health_update32(b, raw, [clock.origin() + 89_000])
+        orc.timers_update(1, G, oo.reply, [clock.origin() + 89_000])
         assert np.array_equal(gpu.timers_read(), orc.timers_read())
         for a, c in zip(gpu.health_read(), orc.health_read()):
             assert np.array_equal(a, c)
