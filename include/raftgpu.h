@@ -795,6 +795,74 @@ int rg_assembler_create(rg_table_t *t, uint32_t max_events, uint32_t max_expired
 int rg_assemble32(rg_assembler_t *a, const rg_arrivals_t *in, const rg_assembled_t *out, int memspace);
 int rg_assembler_destroy(rg_assembler_t *a);
 
+/* ---- ROUTING A DECIDED BATCH BACK TO ARRIVAL ORDER (new symbols only; the ABI stays 6) -----------------------------------------------------------
+ * What a launch leaves of a batch rg_assemble32 made is in the launch's shape: outcome rows at [D][C] in ascending-group order, `origin` the only link back to the
+ * event a cell answers, persist rows scattered under RG_F_PERSIST, a send table of [(P-1)][C] rows that is mostly RG_SEND_NONE, the rare RG_NEED_HOST row found
+ * only by looking at every row. rg_route32 turns that into what the readers of a host want, on the device: the reader that appended event k finds its answer at
+ * index k, the durability journal gets the list of the conversions, a sender thread per peer one contiguous run of the rows it has to ship.
+ *
+ * THE RUN IT ROUTES is the LAST run of assembler `a`: m (arrival events read) and e (expired entries used) are the values THAT run read — the assembler keeps both
+ * in its own device scratch, because a tick that shares the expired_* buffers has overwritten expired_count by the time the route runs, and so that the host need
+ * pass neither. e is 0 for an absent source and for the 0xFFFFFFFF mark. n = min(*count, C) and R = clamp(*rounds, 1, D) are read when the run executes, as the tick
+ * reads them. cell = r * C + i names the cell of row i in round r.
+ *
+ * THE RESULT.
+ *   - ARRIVAL ORDER: cell / row / persist32 of rg_routed_t hold [arrival_capacity] entries. For every k < m: cell[k] is ALWAYS written — the cell whose origin is k,
+ *     RG_ROUTE_NONE for a deferred event and for one with a bad gid; row[k] is that cell's 16 bytes of the `row` column VERBATIM, written iff the event was placed;
+ *     persist32[k] is the cell's persist row, written iff the event was placed and its flags carry RG_F_PERSIST. Entries >= m are NOT TOUCHED. The reader finds
+ *     ready[i] and its send rows from i = cell[k] % C.
+ *   - THE EXPIRED SOURCE: the same three columns, [expired_capacity], all three or none: entry j < e is addressed by the origin 0x80000000 | j, entries >= e are not
+ *     touched.
+ *   - persist_list: {cell, gid} of every cell (r < R, i < n) whose flags carry RG_F_PERSIST, in ascending cell order — round-major, so a group's conversions stay in
+ *     order: what the durability journal consumes. attention: the same for every cell whose status is RG_NEED_HOST.
+ *   - send_list, built only when the send table was given: {row, gid} of every (j, i < n) whose send[j * C + i].kind is RG_SEND_APPEND, RG_SEND_SNAPSHOT or
+ *     RG_SEND_NEED_HOST, follower j ascending, then row ascending; follower j's items are [send_offset[j], send_offset[j + 1]), send_offset[P - 1] is the total: a
+ *     sender thread per peer takes one contiguous run. Rows >= n of the send table were not written by the tick and are not read. Without a send table send_offset is
+ *     not touched and counts[2] is 0.
+ *   - counts[4] = {persist items, attention items, send items, 0}. A count may exceed its list's capacity: the first `capacity` items in the stated order are then
+ *     written and the offsets stay the true ones. List entries beyond what was written are NOT TOUCHED; a capacity of 0 with a NULL list is legal.
+ * Every output is a function of the inputs alone, bit for bit, run after run: the lists are compacted by ballot, popcount and prefix sum, nothing is appended
+ * through an atomic. `origin` must be the column the assembler's last run wrote, unchanged: that no two cells name one event is what makes every routed entry the
+ * store of exactly one lane. An origin column that names an event twice is not refused (RG_MEM_DEVICE does not read it on the host); which of the two cells such an entry
+ * then shows is not defined, and nothing outside the routed columns is written.
+ *
+ * MEMSPACES. RG_MEM_DEVICE: every pointer of both structs is device-visible (rg_dev_alloc / rg_host_alloc); the call is asynchronous on the table's stream,
+ * synchronises nothing and decides nothing on the host from device data — its grids are sized from the capacities and leave early on the n / R / m / e they read.
+ * So rg_assemble32 -> rg_tick2_launch -> rg_route32 queue back to back with no host step between them (the first run of a shape allocates the route's scratch, a
+ * few KiB of per-wavefront counts). RG_MEM_HOST: host arrays, staged in and out, synchronous; only what the run wrote is copied back.
+ * Refused (-1, with a message, before any launch): NULL structs or required columns (gid, count, rounds, origin, row, persist32; cell, row, persist32 of the
+ * arrival order unless arrival_capacity is 0; counts; a list unless its capacity is 0; send_offset with a send table), C = 0 or above the group count, D outside
+ * 1 .. 64, C, D or an arrival / expired capacity that differs from those of the assembler's last run, an assembler that has not run yet, a send table or an
+ * expired triple given in part, an unknown memspace and, in RG_MEM_DEVICE, a pointer that is neither device memory nor page-locked host memory. */
+#define RG_ROUTE_NONE 0xFFFFFFFFu
+typedef struct { uint32_t cell; uint32_t gid; } rg_route_item_t;   /* persist_list, attention */
+typedef struct { uint32_t row;  uint32_t gid; } rg_send_item_t;    /* send_list */
+typedef struct {                       /* the batch rg_assemble32 made, and what the launch that decided it wrote over it */
+    uint32_t              capacity;    /* C */
+    uint32_t              max_rounds;  /* D */
+    const uint32_t       *gid, *count, *rounds, *origin;   /* the assembler's columns: [C], [1], [1], [D][C] */
+    const rg_out32_t     *row;         /* [D][C] */
+    const rg_persist32_t *persist32;   /* [D][C] */
+    const rg_send_head_t *send_head;   /* [C] or NULL */
+    const rg_send_t      *send;        /* [(P-1) * C] or NULL: both or neither */
+} rg_decided_t;
+typedef struct {
+    uint32_t         arrival_capacity;                       /* that of the assembler's last run */
+    uint32_t        *cell;                                   /* [arrival_capacity] */
+    rg_out32_t      *row;                                    /* [arrival_capacity] */
+    rg_persist32_t  *persist32;                              /* [arrival_capacity] */
+    uint32_t         expired_capacity;                       /* with the three columns below: that of the assembler's last run (0 with no expired source) */
+    uint32_t        *expired_cell;                           /* [expired_capacity] or NULL: all three or none (none: a cell that answers a fired ticket is routed nowhere) */
+    rg_out32_t      *expired_row;
+    rg_persist32_t  *expired_persist32;
+    rg_route_item_t *persist_list;  uint32_t persist_capacity;
+    rg_route_item_t *attention;     uint32_t attention_capacity;
+    rg_send_item_t  *send_list;     uint32_t send_capacity;
+    uint32_t        *send_offset;                            /* [P] */
+    uint32_t        *counts;                                 /* [4] */
+} rg_routed_t;
+int rg_route32(rg_assembler_t *a, const rg_decided_t *in, const rg_routed_t *out, int memspace);
+
 /* ---- device memory helpers (so a host without its own HIP binding can keep batches in HBM) --- */
 /* Page-locked host memory for RG_MEM_HOST batches (JNI: wrap it with NewDirectByteBuffer): staging then runs at PCIe
  * speed instead of through the driver's pageable bounce buffers. */

@@ -144,6 +144,21 @@ class CAssembled(C.Structure):         # rg_assembled_t
                 ("stats", C.c_void_p)]
 
 
+class CDecided(C.Structure):           # rg_decided_t
+    _fields_ = [("capacity", C.c_uint32), ("max_rounds", C.c_uint32), ("gid", C.c_void_p), ("count", C.c_void_p), ("rounds", C.c_void_p), ("origin", C.c_void_p),
+                ("row", C.c_void_p), ("persist32", C.c_void_p), ("send_head", C.c_void_p), ("send", C.c_void_p)]
+
+
+class CRouted(C.Structure):            # rg_routed_t
+    _fields_ = [("arrival_capacity", C.c_uint32), ("cell", C.c_void_p), ("row", C.c_void_p), ("persist32", C.c_void_p),
+                ("expired_capacity", C.c_uint32), ("expired_cell", C.c_void_p), ("expired_row", C.c_void_p), ("expired_persist32", C.c_void_p),
+                ("persist_list", C.c_void_p), ("persist_capacity", C.c_uint32), ("attention", C.c_void_p), ("attention_capacity", C.c_uint32),
+                ("send_list", C.c_void_p), ("send_capacity", C.c_uint32), ("send_offset", C.c_void_p), ("counts", C.c_void_p)]
+
+
+ROUTE_NONE = 0xFFFFFFFF                                   # rg_routed_t.cell: a deferred event, or one with a bad gid
+ROUTE_ITEM_DT = np.dtype([("cell", np.uint32), ("gid", np.uint32)])       # rg_route_item_t: persist_list, attention
+SEND_ITEM_DT = np.dtype([("row", np.uint32), ("gid", np.uint32)])         # rg_send_item_t: send_list
 ORIGIN_NONE, ORIGIN_EXPIRED = 0xFFFFFFFF, 0x80000000      # rg_assembled_t.origin: no event in the cell / bit 31 of the id of an entry of the expired source
 EXPIRED_UNTRUSTED = 0xFFFFFFFF                            # *expired_count of a tick whose look-back ran into its bound
 

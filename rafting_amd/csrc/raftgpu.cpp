@@ -18,6 +18,7 @@
 
 #include "rg_device.hpp"
 #include "rg_assemble.hpp"
+#include "rg_route.hpp"
 
 using rg::DevTable;
 using rg::I64x2;
@@ -1040,14 +1041,22 @@ struct rg_assembler {
     rg::AsmParams sc{};                             // the scratch pointers and their capacities; the rest is filled per run
     Staging in_words, in_gid, in_head, in_abcd, ex_gid, ex_epoch;                       // RG_MEM_HOST: the sources ...
     Staging out_gid, out_words, out_head, out_abcd, out_origin, out_deferred;           // ... and the batch
+    bool ran = false;                               // rg_route32 routes the last run: its shape, and the scratch of the route's lists
+    uint32_t last_C = 0, last_D = 0, last_in_cap = 0, last_ex_cap = 0;
+    Staging route_pc, route_ac, route_sc;
+    enum { RT_GID, RT_WORDS, RT_ORIGIN, RT_ROW, RT_PERSIST, RT_SEND, RT_CELL, RT_OROW, RT_OPERSIST, RT_XCELL, RT_XROW, RT_XPERSIST, RT_PLIST, RT_ALIST, RT_SLIST, RT_SOFF,
+           RT_COUNTS, RT_PC, RT_AC, RT_SC, RT_COLUMNS };
+    Staging rt[RT_COLUMNS];                         // RG_MEM_HOST: the columns of rg_decided_t and rg_routed_t, and the lists' count arrays
 };
 
 static void assembler_release(struct rg_assembler *a)
 {
     void *cols[] = {a->sc.cnt, a->sc.bitmap, a->sc.rowof, a->sc.wordoff, a->sc.rowcnt, a->sc.segoff, a->sc.seg, a->sc.flag, a->sc.dcounts, a->sc.big, a->sc.scalars,
                     a->in_words.ptr, a->in_gid.ptr, a->in_head.ptr, a->in_abcd.ptr, a->ex_gid.ptr, a->ex_epoch.ptr,
-                    a->out_gid.ptr, a->out_words.ptr, a->out_head.ptr, a->out_abcd.ptr, a->out_origin.ptr, a->out_deferred.ptr};
+                    a->out_gid.ptr, a->out_words.ptr, a->out_head.ptr, a->out_abcd.ptr, a->out_origin.ptr, a->out_deferred.ptr,
+                    a->route_pc.ptr, a->route_ac.ptr, a->route_sc.ptr};
     for (void *c : cols) if (c) (void)hipFree(c);
+    for (Staging &c : a->rt) if (c.ptr) (void)hipFree(c.ptr);
     *a = rg_assembler{};
 }
 
@@ -1085,7 +1094,7 @@ int rg_assembler_create(rg_table_t *t, uint32_t max_events, uint32_t max_expired
         {(void **)&p.wordoff, (words + 1) * sizeof(uint32_t), false}, {(void **)&p.rowcnt, ((size_t)p.rows_cap + 1) * sizeof(uint32_t), false},
         {(void **)&p.segoff, ((size_t)p.rows_cap + 1) * sizeof(uint32_t), false}, {(void **)&p.seg, (events + 1) * sizeof(uint32_t), false},
         {(void **)&p.flag, events + 1, false}, {(void **)&p.dcounts, (eb * 4 + 1) * sizeof(uint32_t), false}, {(void **)&p.big, (size_t)p.big_cap * sizeof(uint32_t), false},
-        {(void **)&p.scalars, rg::ASM_SCALARS * sizeof(uint32_t), true}};
+        {(void **)&p.scalars, (rg::ASM_SCALARS + 2) * sizeof(uint32_t), true}};
     for (auto &c : cols) {
         hipError_t e = hipMalloc(c.ptr, c.bytes);
         if (e == hipSuccess && c.zero) e = hipMemsetAsync(*c.ptr, 0, c.bytes, t->stream);
@@ -1137,6 +1146,7 @@ int rg_assemble32(rg_assembler_t *a, const rg_arrivals_t *in, const rg_assembled
         p.origin = (uint32_t *)v[12]; p.deferred = (uint32_t *)v[13]; p.stats = (uint32_t *)v[14];
         if (bind(t)) return -2;
         HIP_TRY(t, rg::launch_assemble(p, t->stream));
+        a->ran = true; a->last_C = C; a->last_D = D; a->last_in_cap = in->capacity; a->last_ex_cap = ex_cap;
         return 0;
     }
     if (bind(t)) return -2;
@@ -1168,6 +1178,7 @@ int rg_assemble32(rg_assembler_t *a, const rg_arrivals_t *in, const rg_assembled
     p.gid = (uint32_t *)a->out_gid.ptr; p.count = ow; p.rounds = ow + 1; p.stats = ow + 2;
     p.head = (rg::U32x2 *)a->out_head.ptr; p.abcd = (rg::I32x4 *)a->out_abcd.ptr; p.origin = (uint32_t *)a->out_origin.ptr; p.deferred = (uint32_t *)a->out_deferred.ptr;
     HIP_TRY(t, rg::launch_assemble(p, s));
+    a->ran = true; a->last_C = C; a->last_D = D; a->last_in_cap = in->capacity; a->last_ex_cap = ex_cap;
     uint32_t back[6] = {};
     HIP_TRY(t, hipMemcpyAsync(back, ow, sizeof back, hipMemcpyDeviceToHost, s));
     HIP_TRY(t, hipStreamSynchronize(s));
@@ -1185,6 +1196,128 @@ int rg_assemble32(rg_assembler_t *a, const rg_arrivals_t *in, const rg_assembled
     }
     const uint32_t kept = back[3] < out->deferred_capacity ? back[3] : out->deferred_capacity;
     if (kept) HIP_TRY(t, hipMemcpyAsync(out->deferred, a->out_deferred.ptr, (size_t)kept * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(t, hipStreamSynchronize(s));
+    return 0;
+}
+
+/* ---- routing a decided batch back to arrival order (rg_route32; kernels: rg_route.hpp) ----------------------------------------------- */
+int rg_route32(rg_assembler_t *a, const rg_decided_t *in, const rg_routed_t *out, int memspace)
+{
+    if (!a || !a->t) return -1;
+    rg_table *t = a->t;
+    const char *who = "rg_route32";
+    if (!in || !out) return fail(t, -1, "%s: NULL decided batch or routed columns", who);
+    if (!in->gid || !in->count || !in->rounds || !in->origin || !in->row || !in->persist32)
+        return fail(t, -1, "%s: gid, count, rounds, origin, row and persist32 of the decided batch are required", who);
+    if (!out->counts || (out->arrival_capacity && (!out->cell || !out->row || !out->persist32)) || (out->persist_capacity && !out->persist_list) ||
+        (out->attention_capacity && !out->attention))
+        return fail(t, -1, "%s: cell, row, persist32 and counts of the routed columns are required (and persist_list and attention, unless their capacity is 0)", who);
+    if ((in->send_head != nullptr) != (in->send != nullptr)) return fail(t, -1, "%s: the send table comes as send_head and send, or as neither", who);
+    const bool sends = in->send != nullptr && t->F > 0;
+    if (sends && (!out->send_offset || (out->send_capacity && !out->send_list)))
+        return fail(t, -1, "%s: a send table needs send_offset (and send_list, unless send_capacity is 0)", who);
+    const int triple = (out->expired_cell != nullptr) + (out->expired_row != nullptr) + (out->expired_persist32 != nullptr);
+    if (triple != 0 && triple != 3) return fail(t, -1, "%s: the expired columns come as all three or none", who);
+    const bool expired = triple == 3;
+    if (in->capacity == 0 || in->capacity > t->G) return fail(t, -1, "%s: capacity %u outside 1 .. %u groups", who, in->capacity, t->G);
+    if (in->max_rounds < 1 || in->max_rounds > 64) return fail(t, -1, "%s: max_rounds %u outside 1 .. 64", who, in->max_rounds);
+    if ((uint64_t)in->capacity * in->max_rounds >= 0xFFFFFFFFull)
+        return fail(t, -1, "%s: %u x %u cells: a cell index holds fewer than 2^32 - 1", who, in->capacity, in->max_rounds);
+    if (memspace != RG_MEM_DEVICE && memspace != RG_MEM_HOST) return fail(t, -1, "%s: unknown memspace %d", who, memspace);
+    if (!a->ran) return fail(t, -1, "%s: the assembler has not run yet: there is no run to route", who);
+    if (in->capacity != a->last_C || in->max_rounds != a->last_D)
+        return fail(t, -1, "%s: capacity %u and max_rounds %u, the assembler's last run had %u and %u", who, in->capacity, in->max_rounds, a->last_C, a->last_D);
+    if (out->arrival_capacity != a->last_in_cap)
+        return fail(t, -1, "%s: an arrival capacity of %u, the assembler's last run had %u", who, out->arrival_capacity, a->last_in_cap);
+    if (expired && out->expired_capacity != a->last_ex_cap)
+        return fail(t, -1, "%s: an expired capacity of %u, the assembler's last run had %u", who, out->expired_capacity, a->last_ex_cap);
+    const uint32_t C = in->capacity, D = in->max_rounds, F = t->F, in_cap = out->arrival_capacity, ex_cap = expired ? out->expired_capacity : 0u;
+    rg::RouteParams p{};
+    p.C = C; p.D = D; p.F = F; p.in_cap = in_cap; p.ex_cap = ex_cap; p.last = a->sc.scalars + rg::ASM_LAST; p.span = rg::route_span(C, D, F); p.bpr = (uint32_t)((C + 4ull * p.span - 1) / (4ull * p.span));
+    p.persist_cap = out->persist_capacity; p.attention_cap = out->attention_capacity; p.send_cap = sends ? out->send_capacity : 0u;
+    const size_t W = (size_t)D * p.bpr * 4, Ws = (size_t)F * p.bpr * 4;
+    if (memspace == RG_MEM_DEVICE) {
+        void *v[24] = {};
+        const struct { const void *ptr; const char *what; } cols[] = {
+            {in->gid, "gid"}, {in->count, "count"}, {in->rounds, "rounds"}, {in->origin, "origin"}, {in->row, "the decided row"}, {in->persist32, "the decided persist32"},
+            {in->send_head, "send_head"}, {in->send, "send"}, {out->cell, "cell"}, {out->row, "the routed row"}, {out->persist32, "the routed persist32"},
+            {out->expired_cell, "expired_cell"}, {out->expired_row, "expired_row"}, {out->expired_persist32, "expired_persist32"}, {out->persist_list, "persist_list"},
+            {out->attention, "attention"}, {out->send_list, "send_list"}, {out->send_offset, "send_offset"}, {out->counts, "counts"}};
+        int k = 0;
+        for (const auto &c : cols) if (int rc = device_visible(t, who, c.ptr, c.what, &v[k++])) return rc;
+        if (bind(t)) return -2;
+        if (reserve(t, a->route_pc, (W + 1) * sizeof(uint32_t)) || reserve(t, a->route_ac, (W + 1) * sizeof(uint32_t)) || (sends && reserve(t, a->route_sc, (Ws + 1) * sizeof(uint32_t))))
+            return -2;
+        p.gid = (const uint32_t *)v[0]; p.count = (const uint32_t *)v[1]; p.rounds = (const uint32_t *)v[2]; p.origin = (const uint32_t *)v[3];
+        p.row = (const rg::I32x4 *)v[4]; p.persist32 = (const rg::I32x4 *)v[5]; p.send = sends ? (const rg_send_t *)v[7] : nullptr;
+        p.cell = (uint32_t *)v[8]; p.out_row = (rg::I32x4 *)v[9]; p.out_persist = (rg::I32x4 *)v[10];
+        p.ex_cell = (uint32_t *)v[11]; p.ex_row = (rg::I32x4 *)v[12]; p.ex_persist = (rg::I32x4 *)v[13];
+        p.persist_list = (rg::U32x2 *)v[14]; p.attention = (rg::U32x2 *)v[15]; p.send_list = (rg::U32x2 *)v[16]; p.send_offset = (uint32_t *)v[17]; p.counts = (uint32_t *)v[18];
+        p.pc = (uint32_t *)a->route_pc.ptr; p.ac = (uint32_t *)a->route_ac.ptr; p.sc = (uint32_t *)a->route_sc.ptr;
+        HIP_TRY(t, rg::launch_route(p, t->stream));
+        return 0;
+    }
+    if (bind(t)) return -2;
+    hipStream_t s = t->stream;
+    // host memory: the e and m of the run come back first; then rows 0 .. n - 1 of rounds 0 .. R - 1 go in, and with them what the routed columns hold below m / e — a
+    // placed entry is overwritten, any other travels back as it came —; out come the entries below m / e and what the lists hold
+    uint32_t last[2] = {};
+    HIP_TRY(t, hipMemcpyAsync(last, a->sc.scalars + rg::ASM_LAST, sizeof last, hipMemcpyDeviceToHost, s));
+    HIP_TRY(t, hipStreamSynchronize(s));
+    const uint32_t e = expired ? (last[0] < ex_cap ? last[0] : ex_cap) : 0u, m = last[1] < in_cap ? last[1] : in_cap;
+    const uint32_t n = *in->count < C ? *in->count : C, R = *in->rounds < 1 ? 1u : (*in->rounds < D ? *in->rounds : D);
+    const size_t cells = (size_t)C * D;
+    enum { GID = rg_assembler::RT_GID, WORDS, ORIGIN, ROW, PERSIST, SEND, CELL, OROW, OPERSIST, XCELL, XROW, XPERSIST, PLIST, ALIST, SLIST, SOFF, COUNTS, PC, AC, SC, COLUMNS };
+    static_assert(COLUMNS == rg_assembler::RT_COLUMNS, "one staging buffer per column");
+    const size_t bytes[COLUMNS] = {(size_t)C * 4, 8, cells * 4, cells * 16, cells * 16, sends ? (size_t)F * C * sizeof(rg_send_t) : 0, (size_t)m * 4, (size_t)m * 16, (size_t)m * 16,
+                              (size_t)e * 4, (size_t)e * 16, (size_t)e * 16, (size_t)p.persist_cap * 8, (size_t)p.attention_cap * 8, (size_t)p.send_cap * 8, ((size_t)F + 1) * 4, 16,
+                              (W + 1) * 4, (W + 1) * 4, (Ws + 1) * 4};
+    for (int k = 0; k < COLUMNS; k++) if (reserve(t, a->rt[k], bytes[k] ? bytes[k] : 16)) return -2;
+    auto dev = [&](int k) { return (char *)a->rt[k].ptr; };
+    auto up = [&](int k, const void *src, size_t at, size_t len) { return len ? hipMemcpyAsync(dev(k) + at, (const char *)src + at, len, hipMemcpyHostToDevice, s) : hipSuccess; };
+    auto down = [&](int k, void *dst, size_t at, size_t len) { return len ? hipMemcpyAsync((char *)dst + at, dev(k) + at, len, hipMemcpyDeviceToHost, s) : hipSuccess; };
+    const uint32_t words[2] = {n, R};
+    HIP_TRY(t, hipMemcpyAsync(dev(WORDS), words, sizeof words, hipMemcpyHostToDevice, s));
+    HIP_TRY(t, up(GID, in->gid, 0, (size_t)n * 4));
+    for (uint32_t r = 0; r < R; r++) {
+        const size_t at = (size_t)r * C;
+        HIP_TRY(t, up(ORIGIN, in->origin, at * 4, (size_t)n * 4));
+        HIP_TRY(t, up(ROW, in->row, at * 16, (size_t)n * 16));
+        HIP_TRY(t, up(PERSIST, in->persist32, at * 16, (size_t)n * 16));
+    }
+    for (uint32_t j = 0; sends && j < F; j++) HIP_TRY(t, up(SEND, in->send, (size_t)j * C * sizeof(rg_send_t), (size_t)n * sizeof(rg_send_t)));
+    HIP_TRY(t, up(OROW, out->row, 0, (size_t)m * 16));
+    HIP_TRY(t, up(OPERSIST, out->persist32, 0, (size_t)m * 16));
+    if (expired) {
+        HIP_TRY(t, up(XROW, out->expired_row, 0, (size_t)e * 16));
+        HIP_TRY(t, up(XPERSIST, out->expired_persist32, 0, (size_t)e * 16));
+    }
+    p.count = (const uint32_t *)dev(WORDS); p.rounds = p.count + 1; p.gid = (const uint32_t *)dev(GID); p.origin = (const uint32_t *)dev(ORIGIN);
+    p.row = (const rg::I32x4 *)dev(ROW); p.persist32 = (const rg::I32x4 *)dev(PERSIST); p.send = sends ? (const rg_send_t *)dev(SEND) : nullptr;
+    p.cell = (uint32_t *)dev(CELL); p.out_row = (rg::I32x4 *)dev(OROW); p.out_persist = (rg::I32x4 *)dev(OPERSIST);
+    if (expired) { p.ex_cell = (uint32_t *)dev(XCELL); p.ex_row = (rg::I32x4 *)dev(XROW); p.ex_persist = (rg::I32x4 *)dev(XPERSIST); }
+    p.persist_list = (rg::U32x2 *)dev(PLIST); p.attention = (rg::U32x2 *)dev(ALIST); p.send_list = (rg::U32x2 *)dev(SLIST);
+    p.send_offset = (uint32_t *)dev(SOFF); p.counts = (uint32_t *)dev(COUNTS);
+    p.pc = (uint32_t *)dev(PC); p.ac = (uint32_t *)dev(AC); p.sc = (uint32_t *)dev(SC);
+    HIP_TRY(t, rg::launch_route(p, s));
+    uint32_t counts[4] = {};
+    HIP_TRY(t, hipMemcpyAsync(counts, dev(COUNTS), sizeof counts, hipMemcpyDeviceToHost, s));
+    HIP_TRY(t, hipStreamSynchronize(s));
+    memcpy(out->counts, counts, sizeof counts);
+    HIP_TRY(t, down(CELL, out->cell, 0, (size_t)m * 4));
+    HIP_TRY(t, down(OROW, out->row, 0, (size_t)m * 16));
+    HIP_TRY(t, down(OPERSIST, out->persist32, 0, (size_t)m * 16));
+    if (expired) {
+        HIP_TRY(t, down(XCELL, out->expired_cell, 0, (size_t)e * 4));
+        HIP_TRY(t, down(XROW, out->expired_row, 0, (size_t)e * 16));
+        HIP_TRY(t, down(XPERSIST, out->expired_persist32, 0, (size_t)e * 16));
+    }
+    HIP_TRY(t, down(PLIST, out->persist_list, 0, (size_t)(counts[0] < p.persist_cap ? counts[0] : p.persist_cap) * 8));
+    HIP_TRY(t, down(ALIST, out->attention, 0, (size_t)(counts[1] < p.attention_cap ? counts[1] : p.attention_cap) * 8));
+    if (sends) {
+        HIP_TRY(t, down(SLIST, out->send_list, 0, (size_t)(counts[2] < p.send_cap ? counts[2] : p.send_cap) * 8));
+        HIP_TRY(t, down(SOFF, out->send_offset, 0, ((size_t)F + 1) * 4));
+    }
     HIP_TRY(t, hipStreamSynchronize(s));
     return 0;
 }

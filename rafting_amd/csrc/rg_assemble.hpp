@@ -18,7 +18,7 @@
 //   6. asm_big_rows_kernel  a workgroup per queued row: the D-th smallest position by an 8-bit radix select over an LDS histogram (4 passes over the segment),
 //                           the D positions at or below it ranked in LDS, the rest flagged
 //   7. asm_defer_count / timers_scan_kernel / asm_defer_emit: the flagged positions compacted in S order; the last kernel also writes stats and puts back what the
-//                           run touched of the scratch: cnt and the bitmap word of every event's group, the scalars. The cost of a run follows m + e and groups / 64
+//                           run touched of the scratch: cnt and the bitmap word of every event's group, the scalars — and remembers e and m for rg_route32. The cost of a run follows m + e and groups / 64
 //                           (steps 2, 3), never groups x anything.
 #pragma once
 
@@ -28,7 +28,7 @@ namespace rg {
 
 constexpr uint32_t ASM_SMALL = 64;              // a row with at most this many events is ordered by one lane (<= 64 x 64 cached loads)
 constexpr uint32_t ASM_BIG_BLOCKS = 256;        // workgroups that share the rows with more
-constexpr uint32_t ASM_POOL = 0, ASM_N_BIG = 1, ASM_BAD = 2, ASM_MARK = 3, ASM_SCALARS = ASM_MARK + 65;     // the scratch words `scalars`
+constexpr uint32_t ASM_POOL = 0, ASM_N_BIG = 1, ASM_BAD = 2, ASM_MARK = 3, ASM_SCALARS = ASM_MARK + 65, ASM_LAST = ASM_SCALARS;     // the scratch words `scalars`
 constexpr uint32_t ASM_EXPIRED_ID = 0x80000000u, ASM_NO_EVENT = 0xFFFFFFFFu;
 
 struct AsmParams {
@@ -55,7 +55,7 @@ struct AsmParams {
     uint8_t *flag;                                  // [seg_cap] per position: 1 = deferred
     uint32_t *dcounts;                              // [4 * event workgroups + 1] per-wavefront counts of deferred positions -> offsets, last = their sum
     uint32_t *big;                                  // [big_cap] rows with more than ASM_SMALL events
-    uint32_t *scalars;                              // [ASM_SCALARS]; 0 between runs
+    uint32_t *scalars;                              // [ASM_SCALARS] 0 between runs, + [ASM_LAST .. ASM_LAST + 2) the e and m the last run read, kept for rg_route32 (rg_route.hpp)
     uint32_t rows_cap, seg_cap, big_cap;
 };
 
@@ -266,6 +266,7 @@ __global__ __launch_bounds__(256) void asm_defer_emit_kernel(const AsmParams p)
         const uint32_t deferred = p.dcounts[gridDim.x * 4u], bad = p.scalars[ASM_BAD];
         p.stats[0] = r.T - bad - deferred; p.stats[1] = deferred; p.stats[2] = bad; p.stats[3] = 0u;
         for (uint32_t k = 0; k < ASM_SCALARS; k++) p.scalars[k] = 0u;
+        p.scalars[ASM_LAST] = r.e; p.scalars[ASM_LAST + 1u] = r.m;
     }
     if (!live) return;
     const uint32_t g = asm_gid(p, r, s);            // the scratch this run touched, back to 0 (every event of a group stores the same)

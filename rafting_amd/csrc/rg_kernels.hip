@@ -908,5 +908,8 @@ hipError_t launch_tick_tail(const TickTailParams &p, int followers, hipStream_t 
 // ---- arrival-ordered events into sparse-round batches (rg_assemble32): its kernels use timers_scan_kernel above ---------------------------------------------
 #ifdef RG_TU_MAIN
 #define RG_ASSEMBLE_KERNELS 1
+#define RG_ROUTE_KERNELS 1
 #endif
 #include "rg_assemble.hpp"
+// ---- ... and their results back in arrival order (rg_route32)
+#include "rg_route.hpp"

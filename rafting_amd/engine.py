@@ -31,7 +31,7 @@ def exported_symbols():
     """Every entry point include/raftgpu.h declares."""
     return [
         "rg_abi_version", "rg_table_create", "rg_table_destroy", "rg_last_error", "rg_table_groups",
-        "rg_table_cluster", "rg_table_option", "rg_load_state", "rg_read_state", "rg_submit", "rg_submit32", "rg_submit32c", "rg_submit32c_sparse", "rg_submit32c_sparse_rounds", "rg_outcome32_unpack", "rg_outcome32_unpack_rel", "rg_index_base_set", "rg_index_base_get", "rg_index_base_advance", "rg_index_base_advance32", "rg_batch32_pack_rel", "rg_batch32_pack", "rg_submit_async", "rg_submit_async_packed", "rg_submit_wait", "rg_tick_create", "rg_tick_launch", "rg_tick_wait", "rg_tick_destroy", "rg_tick2_create", "rg_tick2_create_sparse", "rg_tick2_create_sparse_rounds", "rg_tick2_launch", "rg_tick2_wait", "rg_tick2_destroy", "rg_assembler_create", "rg_assemble32", "rg_assembler_destroy", "rg_timers_update32", "rg_health_update32", "rg_sync", "rg_step_kernel", "rg_host_alloc", "rg_host_free", "rg_dev_alloc",
+        "rg_table_cluster", "rg_table_option", "rg_load_state", "rg_read_state", "rg_submit", "rg_submit32", "rg_submit32c", "rg_submit32c_sparse", "rg_submit32c_sparse_rounds", "rg_outcome32_unpack", "rg_outcome32_unpack_rel", "rg_index_base_set", "rg_index_base_get", "rg_index_base_advance", "rg_index_base_advance32", "rg_batch32_pack_rel", "rg_batch32_pack", "rg_submit_async", "rg_submit_async_packed", "rg_submit_wait", "rg_tick_create", "rg_tick_launch", "rg_tick_wait", "rg_tick_destroy", "rg_tick2_create", "rg_tick2_create_sparse", "rg_tick2_create_sparse_rounds", "rg_tick2_launch", "rg_tick2_wait", "rg_tick2_destroy", "rg_assembler_create", "rg_assemble32", "rg_assembler_destroy", "rg_route32", "rg_timers_update32", "rg_health_update32", "rg_sync", "rg_step_kernel", "rg_host_alloc", "rg_host_free", "rg_dev_alloc",
         "rg_dev_free", "rg_copy_to_device", "rg_copy_to_host", "rg_stream", "rg_replicate", "rg_timers_configure", "rg_timers_update",
         "rg_timers_expired", "rg_timers_expired_epochs", "rg_timers_arm", "rg_timers_read", "rg_health_update", "rg_health_failure", "rg_ready", "rg_health_read", "rg_in_flight_read", "rg_in_flight_set",
         "rg_timing_enable",
@@ -134,6 +134,7 @@ def lib():
         L.rg_assembler_create.argtypes = [vp, u32, u32, C.POINTER(vp)]
         L.rg_assemble32.argtypes = [vp, C.POINTER(abi.CArrivals), C.POINTER(abi.CAssembled), i32]
         L.rg_assembler_destroy.argtypes = [vp]
+        L.rg_route32.argtypes = [vp, C.POINTER(abi.CDecided), C.POINTER(abi.CRouted), i32]
         L.rg_timers_update32.argtypes = [vp, u32, vp, vp, vp, i32]
         L.rg_health_update32.argtypes = [vp, u32, vp, vp, vp, i32]
         L.rg_replicate.argtypes = [vp, u32, vp, vp, vp, vp, vp, i32]
@@ -592,6 +593,56 @@ class Assembler:
         b.capacity, b.max_rounds, b.gid, b.count, b.rounds = tick.G, tick.rounds, tick.rows.gid, tick.rows.count, tick.rows.rounds
         b.head, b.abcd, b.origin, b.deferred, b.deferred_capacity, b.stats = tick.io.head, tick.io.abcd, origin, deferred, deferred_capacity, stats
         return b
+
+    def route_device(self, decided, routed):
+        """one RG_MEM_DEVICE run of rg_route32 on the table's stream: the assembler's last run, from two structs whose pointers are device-visible"""
+        self.table._check(lib().rg_route32(self._h, C.byref(decided), C.byref(routed), abi.MEM_DEVICE))
+
+    def decided_for_tick(self, tick, origin):
+        """-> the abi.CDecided over the columns of a Tick2 recorded with sparse_rounds=True (for_tick()'s twin: origin is the column for_tick() was given)"""
+        assert tick.deep and not tick.fixed_depth
+        d = abi.CDecided()
+        d.capacity, d.max_rounds, d.gid, d.count, d.rounds, d.origin = tick.G, tick.rounds, tick.rows.gid, tick.rows.count, tick.rows.rounds, origin
+        d.row, d.persist32, d.send_head, d.send = tick.io.row, tick.io.persist32, tick.io.send_head, tick.io.send
+        return d
+
+    def route(self, gid, count, rounds, origin, row, persist32, capacity, max_rounds, arrival_capacity, expired_capacity=None, send=None,
+              persist_capacity=None, attention_capacity=None, send_capacity=None, fill=0xAB):
+        """one synchronous RG_MEM_HOST run of rg_route32 on numpy arrays (gid [C]; origin / row / persist32 [D * C]; send [(P - 1) * C] or None) ->
+        SimpleNamespace(cell, row, persist32 [arrival_capacity], expired_cell / _row / _persist32 [expired_capacity] (None: no expired columns), persist_list,
+        attention, send_list, send_offset [P], counts [4]); every output held `fill` bytes before the run. A list capacity of None holds every possible item."""
+        import types
+        Cc, D, F = int(capacity), int(max_rounds), self.table.cluster - 1
+        col = lambda a, dt: np.ascontiguousarray(a, dtype=dt)      # noqa: E731
+        gid, origin, row, persist32 = col(gid, np.uint32), col(origin, np.uint32), col(row, abi.OUT32_DT), col(persist32, abi.PERSIST32_DT)
+        words = np.array([count, rounds], np.uint32)
+        d = abi.CDecided()
+        d.capacity, d.max_rounds, d.gid, d.count, d.rounds, d.origin = Cc, D, gid.ctypes.data, words.ctypes.data, words.ctypes.data + 4, origin.ctypes.data
+        d.row, d.persist32 = row.ctypes.data, persist32.ctypes.data
+        if send is not None:
+            send, head = col(send, abi.SEND_DT), np.zeros(max(Cc, 1), abi.SEND_HEAD_DT)
+            d.send_head, d.send = head.ctypes.data, send.ctypes.data
+
+        def blank(dt, k):
+            a = np.zeros(max(int(k), 1), dt)
+            a.view(np.uint8)[:] = fill
+            return a
+        cap = lambda c, most: int(most if c is None else c)      # noqa: E731
+        pcap, acap, scap = cap(persist_capacity, Cc * D), cap(attention_capacity, Cc * D), cap(send_capacity, F * Cc if send is not None else 0)
+        out = types.SimpleNamespace(cell=blank(np.uint32, arrival_capacity), row=blank(abi.OUT32_DT, arrival_capacity), persist32=blank(abi.PERSIST32_DT, arrival_capacity),
+                                    expired_cell=None, expired_row=None, expired_persist32=None, persist_list=blank(abi.ROUTE_ITEM_DT, pcap),
+                                    attention=blank(abi.ROUTE_ITEM_DT, acap), send_list=blank(abi.SEND_ITEM_DT, scap), send_offset=blank(np.uint32, F + 1),
+                                    counts=blank(np.uint32, 4), persist_capacity=pcap, attention_capacity=acap, send_capacity=scap)
+        r = abi.CRouted()
+        r.arrival_capacity, r.cell, r.row, r.persist32 = int(arrival_capacity), out.cell.ctypes.data, out.row.ctypes.data, out.persist32.ctypes.data
+        if expired_capacity is not None:
+            out.expired_cell, out.expired_row, out.expired_persist32 = blank(np.uint32, expired_capacity), blank(abi.OUT32_DT, expired_capacity), blank(abi.PERSIST32_DT, expired_capacity)
+            r.expired_capacity, r.expired_cell, r.expired_row, r.expired_persist32 = (int(expired_capacity), out.expired_cell.ctypes.data, out.expired_row.ctypes.data,
+                                                                                      out.expired_persist32.ctypes.data)
+        r.persist_list, r.persist_capacity, r.attention, r.attention_capacity = (out.persist_list.ctypes.data if pcap else None), pcap, (out.attention.ctypes.data if acap else None), acap
+        r.send_list, r.send_capacity, r.send_offset, r.counts = (out.send_list.ctypes.data if scap else None), scap, out.send_offset.ctypes.data, out.counts.ctypes.data
+        self.table._check(lib().rg_route32(self._h, C.byref(d), C.byref(r), abi.MEM_HOST))
+        return out
 
     def close(self):
         if self._h:
