@@ -28,9 +28,19 @@ struct Staging {
     size_t cap = 0;
 };
 
+// the columns of one batch on the device (RG_MEM_HOST): the wide rows, the compact rows, the outcome in both forms, the per-wavefront list counts of the packed
+// outcome. One set per owner — the table's serial path, every pipeline slot, a recorded tick — freed by walking it
+enum Col { C_GID, C_HEAD, C_AB, C_CD, C_HINT, C_TERMS, C_ABCD32, C_TERMS32, C_REPLY, C_LOGFX, C_PERSIST, C_OUT32, C_PERSIST32, C_COUNTS, C_COLUMNS };
+struct BatchCols {
+    Staging col[C_COLUMNS];
+    Staging &operator[](Col c) { return col[c]; }
+};
+
+// the table's buffers of the small entry points: rg_replicate (heartbeat, in-flight, send heads, send rows), rg_timers_expired, rg_health_failure, rg_ready
+enum Aux { X_HB, X_FL, X_SH, X_SS, X_TGID, X_HGID, X_HSLOT, X_HFLAG, X_HDONE, X_READY, X_COLUMNS };
+
 struct PipeSlot {                               // one batch in flight on the pipelined host-memory path (rg_submit_async)
-    Staging gid, head, ab, cd, hint, terms, reply, logfx, persist;
-    Staging abcd32, terms32, counts;            // rg_submit_async_packed: narrow uploads, per-wavefront list counts
+    BatchCols c;
     hipEvent_t up = nullptr, done = nullptr, down = nullptr;
 };
 
@@ -49,10 +59,10 @@ struct rg_table {
     int has_bases = 0;                          // rg_index_base_set has stored a non-zero base at some time (or RG_OPT_AUTO_INDEX_BASE was switched on)
     int auto_window = 0;                        // rg_table_option(RG_OPT_AUTO_INDEX_BASE): 0 = off
     int compact_any_cluster = 0;                // rg_table_option(RG_OPT_COMPACT_ANY_CLUSTER): the compact formats and the ticks take a cluster above RG_MAX_COMPACT_CLUSTER
-    Staging st_abcd32, st_terms32, st_out32, st_persist32;
     int lanes = -1;                             // -1: pick per launch; 0: split kernel; 64: single-wavefront kernel (RG_SPLIT env forces one)
     uint32_t simds = 1024;                      // SIMDs of the device (CUs x 4)
-    Staging st_gid, st_head, st_ab, st_cd, st_hint, st_terms, st_reply, st_logfx, st_persist, st_hb, st_fl, st_sh, st_ss;
+    BatchCols st;                               // the serial RG_MEM_HOST path: one batch at a time, shared by every entry point that stages one of its columns
+    Staging aux[X_COLUMNS];
     bool timing = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
     size_t ev_used = 0;
@@ -70,11 +80,9 @@ struct rg_table {
     uint32_t *timer_counts = nullptr;           // [waves + 1]: per-wave counts / offsets, last = total
     int64_t election_ms = 900, heartbeat_ms = 300;   // raft1.xml:10-13
     uint64_t timer_seed = 0;
-    Staging st_tgid, st_hgid, st_hslot, st_hflag, st_ready;
     int64_t *health_ok = nullptr, *health_fail = nullptr;   // [F][G] N4b
     int32_t *health_recent = nullptr;
     uint16_t *in_flight = nullptr;              // [F][G] State.requestInFlight; allocated while rg_table_option(RG_OPT_DEVICE_IN_FLIGHT) is 1, nullptr otherwise
-    Staging st_hdone;
     hipStream_t s_in = nullptr, s_out = nullptr; // copy-in / copy-out streams of the pipelined path
     PipeSlot pipe[RG_PIPELINE_DEPTH];
     uint64_t pipe_head = 0, pipe_tail = 0;       // batches submitted / waited for
@@ -128,6 +136,62 @@ static int reserve(rg_table *t, Staging &s, size_t bytes)
     return 0;
 }
 
+// every buffer of an owner, by walking its array (called with the table's device current and its stream idle)
+static void release(Staging *s, size_t n)
+{
+    for (size_t i = 0; i < n; i++) {
+        if (s[i].ptr) (void)hipFree(s[i].ptr);
+        s[i] = Staging{};
+    }
+}
+
+// The typed forms of staging. T is the header's type of an element, D the device code's: the same bytes under two names (rg_ev_pair_t and I64x2, ...).
+// col_up / col_down move `n` elements, from element `at` on, between a host column and the same place of its staging buffer; n == 0 copies nothing. They return
+// the HIP error: a chain recorded under a stream capture, which must always be ended, uses them as they are.
+template <class T>
+static hipError_t col_up(const Staging &s, const T *src, size_t at, size_t n, hipStream_t st)
+{
+    return n ? hipMemcpyAsync((T *)s.ptr + at, src + at, n * sizeof(T), hipMemcpyHostToDevice, st) : hipSuccess;
+}
+
+template <class T>
+static hipError_t col_down(const Staging &s, T *dst, size_t at, size_t n, hipStream_t st)
+{
+    return n ? hipMemcpyAsync(dst + at, (const T *)s.ptr + at, n * sizeof(T), hipMemcpyDeviceToHost, st) : hipSuccess;
+}
+
+// "this host column of n elements, on the device, on this stream": reserve, copy, the typed device pointer
+template <class D, class T>
+static int stage_in(rg_table *t, Staging &s, const T *src, size_t n, hipStream_t st, const D **dev)
+{
+    static_assert(sizeof(D) == sizeof(T), "one element under two names");
+    if (reserve(t, s, n * sizeof(T))) return -2;
+    HIP_TRY(t, col_up(s, src, 0, n, st));
+    *dev = (const D *)s.ptr;
+    return 0;
+}
+
+// an output-only column of n elements: reserve, the typed device pointer
+template <class D>
+static int stage_out(rg_table *t, Staging &s, size_t n, D **dev)
+{
+    if (reserve(t, s, n * sizeof(D))) return -2;
+    *dev = (D *)s.ptr;
+    return 0;
+}
+
+// ... or a column the device only reads, whose copy comes later (a recorded one)
+template <class D>
+static int stage_out(rg_table *t, Staging &s, size_t n, const D **dev) { return stage_out(t, s, n, const_cast<D **>(dev)); }
+
+// "bring n elements back"
+template <class T>
+static int stage_back(rg_table *t, const Staging &s, T *dst, size_t n, hipStream_t st)
+{
+    HIP_TRY(t, col_down(s, dst, 0, n, st));
+    return 0;
+}
+
 static int drain_timing(rg_table *t)
 {
     if (t->ev_used == 0) return 0;
@@ -139,6 +203,104 @@ static int drain_timing(rg_table *t)
         t->t_launches += 1;
     }
     t->ev_used = 0;
+    return 0;
+}
+
+/* a recorded launch: what the once-per-tick path (rg_tick_*) and the device-resident tick (rg_tick2_*) have in common: see include/raftgpu.h */
+struct Recording {
+    rg_table *t = nullptr;
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    uint64_t config_gen = 0;         // the table's at creation: has_bases, require_fence, fast_paths, force_wide are baked into the recorded kernel node
+    bool in_flight = false;
+
+    // everything a recording holds on the device; afterwards it knows no table (called with the table's device current and its stream idle)
+    void release()
+    {
+        if (exec) (void)hipGraphExecDestroy(exec);
+        if (graph) (void)hipGraphDestroy(graph);
+        exec = nullptr; graph = nullptr;
+        t = nullptr;
+    }
+};
+
+struct rg_tick : Recording {         // owns the staging its recorded copies go through
+    BatchCols c;
+    void release() { ::release(c.col, C_COLUMNS); Recording::release(); }
+};
+
+struct rg_tick2 : Recording {};      // owns none: its rows are device-visible where they lie
+
+template <class K>
+static int recording_destroy(K *k, std::vector<K *> rg_table::*list)
+{
+    if (!k) return 0;
+    if (rg_table *t = k->t) {
+        (void)hipSetDevice(t->device);
+        if (t->stream) (void)hipStreamSynchronize(t->stream);
+        std::vector<K *> &live = t->*list;
+        live.erase(std::remove(live.begin(), live.end(), k), live.end());
+        k->release();
+    }
+    delete k;
+    return 0;
+}
+
+static int recording_wait(Recording *k)
+{
+    if (!k || !k->t) return -1;
+    rg_table *t = k->t;
+    HIP_TRY(t, hipSetDevice(t->device));
+    HIP_TRY(t, hipStreamSynchronize(t->stream));
+    k->in_flight = false;
+    return 0;
+}
+
+// a recording is launched under the configuration it was created under; then the table is bound (every batch in flight lands first)
+static int recording_bind(Recording *k, const char *launch, const char *create)
+{
+    if (!k || !k->t) return -1;
+    rg_table *t = k->t;
+    if (k->config_gen != t->config_gen)
+        return fail(t, -1, "%s: the table's options or index bases changed after %s (they are part of the recording): create the tick again", launch, create);
+    return bind(t) ? -2 : 0;
+}
+
+// the tail of a capture on the table's stream, e being what the recorded chain gave: end it (always: an open capture would poison the stream), take the first
+// error, instantiate. On failure the sticky error is cleared; the caller destroys the recording
+static hipError_t recording_finish(Recording *k, hipError_t e)
+{
+    hipGraph_t g = nullptr;
+    const hipError_t e2 = hipStreamEndCapture(k->t->stream, &g);
+    k->graph = g;
+    if (e == hipSuccess) e = e2;
+    if (e == hipSuccess) e = hipGraphInstantiate(&k->exec, k->graph, nullptr, nullptr, 0);
+    if (e != hipSuccess) (void)hipGetLastError();
+    return e;
+}
+
+// the shape of a submission, whatever the format of its rows: what the shape rules and step_params read
+struct Shape {
+    uint32_t rounds, count;
+    const uint32_t *gid;            // nullptr: a dense batch
+    uint64_t entry_count;
+    bool entry_terms;               // the column is there
+};
+
+template <class Batch>
+static Shape shape_of(const Batch *in) { return Shape{in->rounds, in->count, in->gid, in->entry_count, in->entry_terms != nullptr}; }
+
+// At most 64 clock values travel in the kernel arguments of one launch: the rounds of a timer or health update go in chunks of 64. `base` holds what every
+// chunk shares; launch(p, r0) points p at the rows from round r0 on and launches it
+template <class Params, class Launch>
+static int clock_chunks(rg_table *t, uint32_t rounds, const int64_t *now, const Params &base, Launch launch)
+{
+    for (uint32_t r0 = 0; r0 < rounds; r0 += 64) {
+        Params p = base;
+        p.rounds = rounds - r0 < 64 ? rounds - r0 : 64;
+        for (uint32_t k = 0; k < p.rounds; k++) p.now[k] = now[r0 + k];
+        HIP_TRY(t, launch(p, r0));
+    }
     return 0;
 }
 
@@ -194,8 +356,6 @@ int rg_table_option(rg_table_t *t, int option, int value)
     }
 }
 
-static void tick_release(struct rg_tick *k);
-static void tick2_release(struct rg_tick2 *k);
 static void assembler_release(struct rg_assembler *a);
 
 int rg_table_destroy(rg_table_t *t)
@@ -204,21 +364,19 @@ int rg_table_destroy(rg_table_t *t)
     (void)hipSetDevice(t->device);
     if (t->stream) (void)hipStreamSynchronize(t->stream);
     // recordings that outlive their table keep no pointer into it: their launch / wait fail with -1, their destroy only frees the handle
-    for (struct rg_tick *k : t->ticks) tick_release(k);
-    for (struct rg_tick2 *k : t->ticks2) tick2_release(k);
+    for (rg_tick *k : t->ticks) k->release();
+    for (rg_tick2 *k : t->ticks2) k->release();
     for (struct rg_assembler *a : t->assemblers) assembler_release(a);
     t->ticks.clear(); t->ticks2.clear(); t->assemblers.clear();
-    void *cols[] = {t->dt.term_commit, t->dt.epoch, t->dt.window, t->dt.ident, t->dt.elect, t->dt.runs,
-                    t->dt.peer_en, t->dt.peer_m, t->dt.ibase, t->wide_bodies, t->counters, t->st_gid.ptr, t->st_head.ptr, t->st_ab.ptr,
-                    t->st_cd.ptr, t->st_hint.ptr, t->st_terms.ptr, t->st_reply.ptr, t->st_logfx.ptr,
-                    t->st_persist.ptr, t->st_hb.ptr, t->st_fl.ptr, t->st_sh.ptr, t->st_ss.ptr, t->timer_deadline, t->timer_epoch, t->tick_masks, t->tick_ticket,
-                    t->timer_counts, t->st_tgid.ptr, t->st_hgid.ptr, t->st_hslot.ptr, t->st_hflag.ptr, t->st_ready.ptr, t->health_ok,
-                    t->health_fail, t->health_recent, t->in_flight, t->st_hdone.ptr, t->st_abcd32.ptr, t->st_terms32.ptr, t->st_out32.ptr, t->st_persist32.ptr};
+    void *cols[] = {t->dt.term_commit, t->dt.epoch, t->dt.window, t->dt.ident, t->dt.elect, t->dt.runs, t->dt.peer_en, t->dt.peer_m, t->dt.ibase, t->wide_bodies,
+                    t->counters, t->timer_deadline, t->timer_epoch, t->tick_masks, t->tick_ticket, t->timer_counts, t->health_ok, t->health_fail, t->health_recent,
+                    t->in_flight};
     for (void *c : cols) if (c) (void)hipFree(c);
+    release(t->st.col, C_COLUMNS);
+    release(t->aux, X_COLUMNS);
     for (PipeSlot &sl : t->pipe) {
         if (sl.down) (void)hipEventSynchronize(sl.down);
-        for (Staging *st : {&sl.gid, &sl.head, &sl.ab, &sl.cd, &sl.hint, &sl.terms, &sl.reply, &sl.logfx, &sl.persist, &sl.abcd32, &sl.terms32, &sl.counts})
-            if (st->ptr) (void)hipFree(st->ptr);
+        release(sl.c.col, C_COLUMNS);
         for (hipEvent_t ev : {sl.up, sl.done, sl.down}) if (ev) (void)hipEventDestroy(ev);
     }
     if (t->s_in) (void)hipStreamDestroy(t->s_in);
@@ -505,37 +663,52 @@ static int compact_ok(rg_table *t, const char *who)
     return 0;
 }
 
-// list_rounds: the caller takes a list of groups with any number of rounds (rg_submit32c_sparse_rounds, rg_tick2_create_sparse_rounds)
-static int check_batch(rg_table *t, const rg_batch_t *in, const rg_outcome_t *out, bool host_memory, bool list_rounds = false)
+// a list of groups in host memory names groups of the table, strictly ascending -> 0, or the rule the first offending row breaks: 1 = out of range,
+// 2 = not ascending; *row is that row. (Each entry point words the refusal itself.)
+static int bad_gid_list(const uint32_t *gid, uint32_t count, uint32_t groups, uint32_t *row)
 {
-    if (!in || !out) return fail(t, -1, "rg_submit: NULL batch or outcome");
-    if (!in->head || !in->ab || !in->cd || !out->reply || !out->logfx || !out->persist)
-        return fail(t, -1, "rg_submit: head/ab/cd/reply/logfx/persist are required");
-    if (in->rounds == 0) return fail(t, -1, "rg_submit: rounds must be >= 1");
-    const bool sparse = in->gid != nullptr;
-    if (sparse) {
-        if (in->rounds != 1 && !list_rounds) return fail(t, -1, "rg_submit: sparse batches carry exactly one round");
-        if (in->count > t->G) return fail(t, -1, "rg_submit: %u rows for %u groups", in->count, t->G);
-    } else if (in->count != t->G) {
-        return fail(t, -1, "rg_submit: dense batch has %u rows per round, table has %u groups", in->count, t->G);
-    }
-    if (in->entry_count && !in->entry_terms) return fail(t, -1, "rg_submit: entry_count without entry_terms");
-    if (in->entry_count > (1ull << 29)) return fail(t, -1, "rg_submit: at most 2^29 entry terms per batch (%llu given)", (unsigned long long)in->entry_count);
-    if (sparse && host_memory) {
-        for (uint32_t i = 0; i < in->count; i++) {
-            if (in->gid[i] >= t->G) return fail(t, -1, "rg_submit: gid[%u]=%u out of range", i, in->gid[i]);
-            if (i && in->gid[i] <= in->gid[i - 1]) return fail(t, -1, "rg_submit: gid must be strictly ascending (row %u)", i);
-        }
+    for (uint32_t i = 0; i < count; i++) {
+        const int why = gid[i] >= groups ? 1 : (i && gid[i] <= gid[i - 1]) ? 2 : 0;
+        if (why) { *row = i; return why; }
     }
     return 0;
 }
 
-static rg::StepParams step_params(rg_table *t, const rg_batch_t *in)
+// the same shape rules for every submission (rounds, count, gid list, entry bound); the refusals say rg_submit whichever entry point was called
+// list_rounds: the caller takes a list of groups with any number of rounds (rg_submit32c_sparse_rounds, rg_tick2_create_sparse_rounds)
+static int check_shape(rg_table *t, const Shape &in, bool host_memory, bool list_rounds = false)
+{
+    if (in.rounds == 0) return fail(t, -1, "rg_submit: rounds must be >= 1");
+    const bool sparse = in.gid != nullptr;
+    if (sparse) {
+        if (in.rounds != 1 && !list_rounds) return fail(t, -1, "rg_submit: sparse batches carry exactly one round");
+        if (in.count > t->G) return fail(t, -1, "rg_submit: %u rows for %u groups", in.count, t->G);
+    } else if (in.count != t->G) {
+        return fail(t, -1, "rg_submit: dense batch has %u rows per round, table has %u groups", in.count, t->G);
+    }
+    if (in.entry_count && !in.entry_terms) return fail(t, -1, "rg_submit: entry_count without entry_terms");
+    if (in.entry_count > (1ull << 29)) return fail(t, -1, "rg_submit: at most 2^29 entry terms per batch (%llu given)", (unsigned long long)in.entry_count);
+    uint32_t i = 0;
+    if (sparse && host_memory)
+        if (const int why = bad_gid_list(in.gid, in.count, t->G, &i))
+            return why == 1 ? fail(t, -1, "rg_submit: gid[%u]=%u out of range", i, in.gid[i]) : fail(t, -1, "rg_submit: gid must be strictly ascending (row %u)", i);
+    return 0;
+}
+
+static int check_batch(rg_table *t, const rg_batch_t *in, const rg_outcome_t *out, bool host_memory)
+{
+    if (!in || !out) return fail(t, -1, "rg_submit: NULL batch or outcome");
+    if (!in->head || !in->ab || !in->cd || !out->reply || !out->logfx || !out->persist)
+        return fail(t, -1, "rg_submit: head/ab/cd/reply/logfx/persist are required");
+    return check_shape(t, shape_of(in), host_memory);
+}
+
+static rg::StepParams step_params(rg_table *t, const Shape &in)
 {
     rg::StepParams p{};
     p.t = t->dt;
-    p.rounds = in->rounds; p.count = in->count; p.stride = in->count;
-    p.entry_count = in->entry_count;
+    p.rounds = in.rounds; p.count = in.count; p.stride = in.count;
+    p.entry_count = in.entry_count;
     p.counters = t->counters;
     p.wide_bodies = t->wide_bodies;
     p.self = (int32_t)t->self; p.cluster = (int32_t)t->P; p.majority = (int32_t)(t->P / 2 + 1); p.pre_vote = t->pre_vote;
@@ -545,6 +718,40 @@ static rg::StepParams step_params(rg_table *t, const rg_batch_t *in)
     p.has_bases = t->has_bases;
     p.auto_window = t->auto_window;
     return p;
+}
+
+// A batch in host memory onto the device, on stream s, into the columns c of its owner (the table, a pipeline slot): the inputs are staged and p reads them.
+// The wide rows: head / ab / cd, the gid list of a list of groups, the hint column and the entry terms where the batch has them ...
+static int upload_wide(rg_table *t, BatchCols &c, const rg_batch_t *in, hipStream_t s, rg::StepParams &p)
+{
+    const size_t rows = (size_t)in->rounds * in->count;
+    if (stage_in(t, c[C_HEAD], in->head, rows, s, &p.head) || stage_in(t, c[C_AB], in->ab, rows, s, &p.ab) || stage_in(t, c[C_CD], in->cd, rows, s, &p.cd)) return -2;
+    if (in->gid && stage_in(t, c[C_GID], in->gid, in->count, s, &p.gid)) return -2;
+    if (in->hint && stage_in(t, c[C_HINT], in->hint, rows, s, &p.hint)) return -2;
+    if (in->entry_count && stage_in(t, c[C_TERMS], in->entry_terms, in->entry_count, s, &p.entry_terms)) return -2;
+    return 0;
+}
+
+// ... and the compact rows: head / abcd, the gid list, the 32-bit entry terms. The compact-format kernel reads the rows as they arrived: no widening pass
+static int upload_compact(rg_table *t, BatchCols &c, const rg_batch32_t *in, hipStream_t s, rg::StepParams &p)
+{
+    const size_t rows = (size_t)in->rounds * in->count;
+    if (stage_in(t, c[C_HEAD], in->head, rows, s, &p.head) || stage_in(t, c[C_ABCD32], in->abcd, rows, s, &p.abcd32)) return -2;
+    if (in->gid && stage_in(t, c[C_GID], in->gid, in->count, s, &p.gid)) return -2;
+    if (in->entry_count && stage_in(t, c[C_TERMS32], in->entry_terms, in->entry_count, s, &p.entry_terms32)) return -2;
+    return 0;
+}
+
+// the wide outcome columns of `rows` rows for p to write ...
+static int outcome_wide(rg_table *t, BatchCols &c, size_t rows, rg::StepParams &p)
+{
+    return stage_out(t, c[C_REPLY], rows, &p.reply) || stage_out(t, c[C_LOGFX], rows, &p.logfx) || stage_out(t, c[C_PERSIST], rows, &p.persist) ? -2 : 0;
+}
+
+// ... and back into the caller's reply / logfx / persist, on stream s
+static int download_wide(rg_table *t, BatchCols &c, const rg_outcome_t &out, size_t rows, hipStream_t s)
+{
+    return stage_back(t, c[C_REPLY], out.reply, rows, s) || stage_back(t, c[C_LOGFX], out.logfx, rows, s) || stage_back(t, c[C_PERSIST], out.persist, rows, s) ? -2 : 0;
 }
 
 static int pipeline_ready(rg_table *t);
@@ -560,39 +767,16 @@ int rg_submit_async(rg_table_t *t, const rg_batch_t *in, const rg_outcome_t *out
     PipeSlot &sl = t->pipe[t->pipe_head % RG_PIPELINE_DEPTH];
     const bool sparse = in->gid != nullptr;
     const size_t rows = (size_t)in->rounds * in->count;
-    rg::StepParams p = step_params(t, in);
-    if (reserve(t, sl.head, rows * sizeof(rg_ev_head_t)) || reserve(t, sl.ab, rows * sizeof(I64x2)) || reserve(t, sl.cd, rows * sizeof(I64x2)) ||
-        reserve(t, sl.reply, rows * sizeof(rg_reply_t)) || reserve(t, sl.logfx, rows * sizeof(I64x2)) || reserve(t, sl.persist, rows * sizeof(rg_persist_t)))
-        return -2;
+    rg::StepParams p = step_params(t, shape_of(in));
     hipStream_t si = t->s_in, so = t->s_out;
-    HIP_TRY(t, hipMemcpyAsync(sl.head.ptr, in->head, rows * sizeof(rg_ev_head_t), hipMemcpyHostToDevice, si));
-    HIP_TRY(t, hipMemcpyAsync(sl.ab.ptr, in->ab, rows * sizeof(I64x2), hipMemcpyHostToDevice, si));
-    HIP_TRY(t, hipMemcpyAsync(sl.cd.ptr, in->cd, rows * sizeof(I64x2), hipMemcpyHostToDevice, si));
-    p.head = (const rg_ev_head_t *)sl.head.ptr; p.ab = (const I64x2 *)sl.ab.ptr; p.cd = (const I64x2 *)sl.cd.ptr;
-    if (sparse) {
-        if (reserve(t, sl.gid, in->count * sizeof(uint32_t))) return -2;
-        HIP_TRY(t, hipMemcpyAsync(sl.gid.ptr, in->gid, in->count * sizeof(uint32_t), hipMemcpyHostToDevice, si));
-        p.gid = (const uint32_t *)sl.gid.ptr;
-    }
-    if (in->hint) {
-        if (reserve(t, sl.hint, rows * sizeof(I64x2))) return -2;
-        HIP_TRY(t, hipMemcpyAsync(sl.hint.ptr, in->hint, rows * sizeof(I64x2), hipMemcpyHostToDevice, si));
-        p.hint = (const I64x2 *)sl.hint.ptr;
-    }
-    if (in->entry_count) {
-        if (reserve(t, sl.terms, in->entry_count * sizeof(int64_t))) return -2;
-        HIP_TRY(t, hipMemcpyAsync(sl.terms.ptr, in->entry_terms, in->entry_count * sizeof(int64_t), hipMemcpyHostToDevice, si));
-        p.entry_terms = (const int64_t *)sl.terms.ptr;
-    }
+    if (int rc = outcome_wide(t, sl.c, rows, p)) return rc;
+    if (int rc = upload_wide(t, sl.c, in, si, p)) return rc;
     HIP_TRY(t, hipEventRecord(sl.up, si));
     HIP_TRY(t, hipStreamWaitEvent(t->stream, sl.up, 0));                  // the kernel of this batch needs its upload ...
-    p.reply = (rg_reply_t *)sl.reply.ptr; p.logfx = (I64x2 *)sl.logfx.ptr; p.persist = (rg_persist_t *)sl.persist.ptr;
     if (int rc = launch(t, p, sparse)) return rc;                          // ... and, being on the table's stream, runs after the batch before it
     HIP_TRY(t, hipEventRecord(sl.done, t->stream));
     HIP_TRY(t, hipStreamWaitEvent(so, sl.done, 0));
-    HIP_TRY(t, hipMemcpyAsync(out->reply, sl.reply.ptr, rows * sizeof(rg_reply_t), hipMemcpyDeviceToHost, so));
-    HIP_TRY(t, hipMemcpyAsync(out->logfx, sl.logfx.ptr, rows * sizeof(I64x2), hipMemcpyDeviceToHost, so));
-    HIP_TRY(t, hipMemcpyAsync(out->persist, sl.persist.ptr, rows * sizeof(rg_persist_t), hipMemcpyDeviceToHost, so));
+    if (int rc = download_wide(t, sl.c, *out, rows, so)) return rc;
     HIP_TRY(t, hipEventRecord(sl.down, so));
     t->pipe_head += 1;
     return 0;
@@ -621,13 +805,7 @@ int rg_submit_async_packed(rg_table_t *t, const rg_batch32_t *in, const rg_outco
     if (!in->head || !in->abcd || !out->reply || !out->counts || (out->logfx_cap && !out->logfx) || (out->persist_cap && !out->persist))
         return fail(t, -1, "rg_submit_async_packed: head, abcd, reply, counts and every list with a capacity are required");
     if (in->entry_count && !in->entry_terms) return fail(t, -1, "rg_submit_async_packed: entry_count %llu without entry_terms", (unsigned long long)in->entry_count);
-    rg_batch_t wide{};                              // the same shape rules as every other submission (rounds, count, gid list, entry bound)
-    wide.rounds = in->rounds; wide.count = in->count; wide.gid = in->gid; wide.head = in->head;
-    wide.ab = wide.cd = reinterpret_cast<const rg_ev_pair_t *>(in->abcd);      // presence only: check_batch does not read event fields
-    wide.entry_terms = reinterpret_cast<const int64_t *>(in->entry_terms); wide.entry_count = in->entry_count;
-    rg_logfx_t dummy_l; rg_persist_t dummy_p;
-    const rg_outcome_t shape{out->reply, &dummy_l, &dummy_p};
-    if (int rc = check_batch(t, &wide, &shape, true)) return rc;
+    if (int rc = check_shape(t, shape_of(in), true)) return rc;
     if (in->count == 0) { out->counts[0] = out->counts[1] = 0; return 0; }
     const size_t rows64 = (size_t)in->rounds * in->count;
     if (rows64 >= (1ull << 31)) return fail(t, -1, "rg_submit_async_packed: %zu rows in one batch (limit 2^31 - 1)", rows64);
@@ -644,78 +822,28 @@ int rg_submit_async_packed(rg_table_t *t, const rg_batch32_t *in, const rg_outco
     PipeSlot &sl = t->pipe[t->pipe_head % RG_PIPELINE_DEPTH];
     const bool sparse = in->gid != nullptr;
     const uint32_t rows = (uint32_t)rows64, waves = (rows + 63u) / 64u;
-    rg::StepParams p = step_params(t, &wide);
-    if (reserve(t, sl.head, rows64 * sizeof(rg_ev_head_t)) || reserve(t, sl.abcd32, rows64 * sizeof(rg_ev_quad32_t)) ||
-        reserve(t, sl.reply, rows64 * sizeof(rg_reply_t)) || reserve(t, sl.logfx, rows64 * sizeof(I64x2)) ||
-        reserve(t, sl.persist, rows64 * sizeof(rg_persist_t)) || reserve(t, sl.counts, (size_t)2 * waves * sizeof(uint32_t)))
-        return -2;
+    rg::StepParams p = step_params(t, shape_of(in));
+    uint32_t *wave_counts = nullptr;
     hipStream_t si = t->s_in, so = t->s_out;
-    HIP_TRY(t, hipMemcpyAsync(sl.head.ptr, in->head, rows64 * sizeof(rg_ev_head_t), hipMemcpyHostToDevice, si));
-    HIP_TRY(t, hipMemcpyAsync(sl.abcd32.ptr, in->abcd, rows64 * sizeof(rg_ev_quad32_t), hipMemcpyHostToDevice, si));
-    if (sparse) {
-        if (reserve(t, sl.gid, in->count * sizeof(uint32_t))) return -2;
-        HIP_TRY(t, hipMemcpyAsync(sl.gid.ptr, in->gid, in->count * sizeof(uint32_t), hipMemcpyHostToDevice, si));
-        p.gid = (const uint32_t *)sl.gid.ptr;
-    }
-    if (in->entry_count) {
-        if (reserve(t, sl.terms32, in->entry_count * sizeof(int32_t))) return -2;
-        HIP_TRY(t, hipMemcpyAsync(sl.terms32.ptr, in->entry_terms, in->entry_count * sizeof(int32_t), hipMemcpyHostToDevice, si));
-    }
+    if (int rc = outcome_wide(t, sl.c, rows64, p)) return rc;
+    if (stage_out(t, sl.c[C_COUNTS], (size_t)2 * waves, &wave_counts)) return -2;
+    if (int rc = upload_compact(t, sl.c, in, si, p)) return rc;
     HIP_TRY(t, hipEventRecord(sl.up, si));
     HIP_TRY(t, hipStreamWaitEvent(t->stream, sl.up, 0));
-    // the compact-format kernel reads the rows as they arrived: no widening pass
-    p.head = (const rg_ev_head_t *)sl.head.ptr; p.abcd32 = (const rg::I32x4 *)sl.abcd32.ptr;
-    p.hint = nullptr;
-    p.entry_terms32 = in->entry_count ? (const int32_t *)sl.terms32.ptr : nullptr;
-    p.reply = (rg_reply_t *)sl.reply.ptr; p.logfx = (I64x2 *)sl.logfx.ptr; p.persist = (rg_persist_t *)sl.persist.ptr;
     if (int rc = launch(t, p, sparse)) return rc;
-    HIP_TRY(t, rg::launch_outcome_count(p.reply, rows, (uint32_t *)sl.counts.ptr, (uint32_t *)d_counts, t->stream));
+    HIP_TRY(t, rg::launch_outcome_count(p.reply, rows, wave_counts, (uint32_t *)d_counts, t->stream));
     HIP_TRY(t, hipEventRecord(sl.done, t->stream));
     HIP_TRY(t, hipStreamWaitEvent(so, sl.done, 0));
     // the scatter is link-bound (it writes host memory): on the copy-out stream, so the next batch's kernels do not queue behind it
-    HIP_TRY(t, rg::launch_outcome_emit(p.reply, p.logfx, p.persist, rows, (const uint32_t *)sl.counts.ptr, (I64x2 *)d_logfx, out->logfx_cap,
-                                       (rg_persist_t *)d_persist, out->persist_cap, so));
-    HIP_TRY(t, hipMemcpyAsync(out->reply, sl.reply.ptr, rows64 * sizeof(rg_reply_t), hipMemcpyDeviceToHost, so));
+    HIP_TRY(t, rg::launch_outcome_emit(p.reply, p.logfx, p.persist, rows, wave_counts, (I64x2 *)d_logfx, out->logfx_cap, (rg_persist_t *)d_persist, out->persist_cap, so));
+    if (int rc = stage_back(t, sl.c[C_REPLY], out->reply, rows64, so)) return rc;
     HIP_TRY(t, hipEventRecord(sl.down, so));
     t->pipe_head += 1;
     return 0;
 }
 
 /* the once-per-tick path: see include/raftgpu.h */
-struct rg_tick {
-    rg_table *t = nullptr;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    Staging head, abcd, gid, terms, reply, logfx, persist, counts;
-    uint64_t config_gen = 0;         // the table's at creation: has_bases, require_fence, fast_paths, force_wide are baked into the recorded kernel node
-    bool in_flight = false;
-};
-
-// everything a recording holds on the device; afterwards it knows no table (called with the table's device current and its stream idle)
-static void tick_release(struct rg_tick *k)
-{
-    if (k->exec) (void)hipGraphExecDestroy(k->exec);
-    if (k->graph) (void)hipGraphDestroy(k->graph);
-    k->exec = nullptr; k->graph = nullptr;
-    for (Staging *st : {&k->head, &k->abcd, &k->gid, &k->terms, &k->reply, &k->logfx, &k->persist, &k->counts}) {
-        if (st->ptr) (void)hipFree(st->ptr);
-        st->ptr = nullptr; st->cap = 0;
-    }
-    k->t = nullptr;
-}
-
-int rg_tick_destroy(rg_tick_t *k)
-{
-    if (!k) return 0;
-    if (rg_table *t = k->t) {
-        (void)hipSetDevice(t->device);
-        if (t->stream) (void)hipStreamSynchronize(t->stream);
-        t->ticks.erase(std::remove(t->ticks.begin(), t->ticks.end(), k), t->ticks.end());
-        tick_release(k);
-    }
-    delete k;
-    return 0;
-}
+int rg_tick_destroy(rg_tick_t *k) { return recording_destroy(k, &rg_table::ticks); }
 
 // a buffer a recorded copy replays from / into must be page-locked: a pageable one is either rejected late by the capture with an opaque error, or
 // captured with undefined semantics
@@ -737,16 +865,10 @@ int rg_tick_create(rg_table_t *t, const rg_batch32_t *in, const rg_outcome_packe
     if (!in->head || !in->abcd || !out->reply || !out->counts || (out->logfx_cap && !out->logfx) || (out->persist_cap && !out->persist))
         return fail(t, -1, "rg_tick_create: head, abcd, reply, counts and every list with a capacity are required");
     if (in->entry_count && !in->entry_terms) return fail(t, -1, "rg_tick_create: entry_count %llu without entry_terms", (unsigned long long)in->entry_count);
-    rg_batch_t wide{};
-    wide.rounds = in->rounds; wide.count = in->count; wide.gid = nullptr; wide.head = in->head;      // (a sparse gid list is read at every launch, not now)
-    wide.ab = wide.cd = reinterpret_cast<const rg_ev_pair_t *>(in->abcd);
-    wide.entry_terms = reinterpret_cast<const int64_t *>(in->entry_terms); wide.entry_count = in->entry_count;
-    rg_logfx_t dummy_l; rg_persist_t dummy_p;
-    const rg_outcome_t shape{out->reply, &dummy_l, &dummy_p};
-    if (in->gid) {
+    if (in->gid) {                                          // (a sparse gid list is read at every launch, not now: only the round and row counts are checked here)
         if (in->rounds != 1) return fail(t, -1, "rg_tick_create: sparse batches carry exactly one round");
         if (in->count > t->G || in->count == 0) return fail(t, -1, "rg_tick_create: %u rows for %u groups", in->count, t->G);
-    } else if (int rc = check_batch(t, &wide, &shape, true)) return rc;
+    } else if (int rc = check_shape(t, shape_of(in), true)) return rc;
     if (in->rounds == 0 || in->count == 0) return fail(t, -1, "rg_tick_create: an empty shape");
     const size_t rows64 = (size_t)in->rounds * in->count;
     if (rows64 >= (1ull << 31)) return fail(t, -1, "rg_tick_create: %zu rows in one batch (limit 2^31 - 1)", rows64);
@@ -766,35 +888,27 @@ int rg_tick_create(rg_table_t *t, const rg_batch32_t *in, const rg_outcome_packe
     k->config_gen = t->config_gen;
     const uint32_t rows = (uint32_t)rows64, waves = (rows + 63u) / 64u;
     const bool sparse = in->gid != nullptr;
-    if (reserve(t, k->head, rows64 * sizeof(rg_ev_head_t)) || reserve(t, k->abcd, rows64 * sizeof(rg_ev_quad32_t)) || reserve(t, k->reply, rows64 * sizeof(rg_reply_t)) ||
-        reserve(t, k->logfx, rows64 * sizeof(I64x2)) || reserve(t, k->persist, rows64 * sizeof(rg_persist_t)) || reserve(t, k->counts, (size_t)2 * waves * sizeof(uint32_t)) ||
-        (sparse && reserve(t, k->gid, in->count * sizeof(uint32_t))) || (in->entry_count && reserve(t, k->terms, in->entry_count * sizeof(int32_t)))) {
+    rg::StepParams p = step_params(t, shape_of(in));
+    BatchCols &c = k->c;
+    uint32_t *wave_counts = nullptr;
+    if (outcome_wide(t, c, rows64, p) || stage_out(t, c[C_COUNTS], (size_t)2 * waves, &wave_counts) || stage_out(t, c[C_HEAD], rows64, &p.head) ||
+        stage_out(t, c[C_ABCD32], rows64, &p.abcd32) || (sparse && stage_out(t, c[C_GID], in->count, &p.gid)) ||
+        (in->entry_count && stage_out(t, c[C_TERMS32], in->entry_count, &p.entry_terms32))) {
         rg_tick_destroy(k);
         return -2;
     }
-    rg::StepParams p = step_params(t, &wide);
-    p.head = (const rg_ev_head_t *)k->head.ptr; p.abcd32 = (const rg::I32x4 *)k->abcd.ptr;
-    p.gid = sparse ? (const uint32_t *)k->gid.ptr : nullptr;
-    p.entry_terms32 = in->entry_count ? (const int32_t *)k->terms.ptr : nullptr;
-    p.reply = (rg_reply_t *)k->reply.ptr; p.logfx = (I64x2 *)k->logfx.ptr; p.persist = (rg_persist_t *)k->persist.ptr;
+    // the copies are recorded: the chain keeps going to the end of the capture whatever fails, and carries the first error there
     hipStream_t s = t->stream;
     hipError_t e = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
-    if (e == hipSuccess) e = hipMemcpyAsync(k->head.ptr, in->head, rows64 * sizeof(rg_ev_head_t), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(k->abcd.ptr, in->abcd, rows64 * sizeof(rg_ev_quad32_t), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && sparse) e = hipMemcpyAsync(k->gid.ptr, in->gid, in->count * sizeof(uint32_t), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && in->entry_count) e = hipMemcpyAsync(k->terms.ptr, in->entry_terms, in->entry_count * sizeof(int32_t), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = col_up(c[C_HEAD], in->head, 0, rows64, s);
+    if (e == hipSuccess) e = col_up(c[C_ABCD32], in->abcd, 0, rows64, s);
+    if (e == hipSuccess && sparse) e = col_up(c[C_GID], in->gid, 0, in->count, s);
+    if (e == hipSuccess) e = col_up(c[C_TERMS32], in->entry_terms, 0, in->entry_count, s);
     if (e == hipSuccess) e = rg::launch_step(p, (int)t->F, sparse, 32, s);
-    if (e == hipSuccess) e = rg::launch_outcome_count(p.reply, rows, (uint32_t *)k->counts.ptr, (uint32_t *)d_counts, s);
-    if (e == hipSuccess) e = rg::launch_outcome_emit(p.reply, p.logfx, p.persist, rows, (const uint32_t *)k->counts.ptr, (I64x2 *)d_logfx, out->logfx_cap,
-                                                     (rg_persist_t *)d_persist, out->persist_cap, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(out->reply, k->reply.ptr, rows64 * sizeof(rg_reply_t), hipMemcpyDeviceToHost, s);
-    hipGraph_t g = nullptr;
-    const hipError_t e2 = hipStreamEndCapture(s, &g);           // (always: an open capture would poison the stream)
-    k->graph = g;
-    if (e == hipSuccess) e = e2;
-    if (e == hipSuccess) e = hipGraphInstantiate(&k->exec, k->graph, nullptr, nullptr, 0);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
+    if (e == hipSuccess) e = rg::launch_outcome_count(p.reply, rows, wave_counts, (uint32_t *)d_counts, s);
+    if (e == hipSuccess) e = rg::launch_outcome_emit(p.reply, p.logfx, p.persist, rows, wave_counts, (I64x2 *)d_logfx, out->logfx_cap, (rg_persist_t *)d_persist, out->persist_cap, s);
+    if (e == hipSuccess) e = col_down(c[C_REPLY], out->reply, 0, rows64, s);
+    if ((e = recording_finish(k, e)) != hipSuccess) {
         rg_tick_destroy(k);
         return fail(t, -2, "rg_tick_create: %s", hipGetErrorString(e));
     }
@@ -805,59 +919,21 @@ int rg_tick_create(rg_table_t *t, const rg_batch32_t *in, const rg_outcome_packe
 
 int rg_tick_launch(rg_tick_t *k)
 {
-    if (!k || !k->t) return -1;
+    if (int rc = recording_bind(k, "rg_tick_launch", "rg_tick_create")) return rc;
     rg_table *t = k->t;
-    if (k->config_gen != t->config_gen)
-        return fail(t, -1, "rg_tick_launch: the table's options or index bases changed after rg_tick_create (they are part of the recording): create the tick again");
-    if (bind(t)) return -2;
     if (k->in_flight) { HIP_TRY(t, hipStreamSynchronize(t->stream)); k->in_flight = false; }
     HIP_TRY(t, hipGraphLaunch(k->exec, t->stream));
     k->in_flight = true;
     return 0;
 }
 
-int rg_tick_wait(rg_tick_t *k)
-{
-    if (!k || !k->t) return -1;
-    rg_table *t = k->t;
-    HIP_TRY(t, hipSetDevice(t->device));
-    HIP_TRY(t, hipStreamSynchronize(t->stream));
-    k->in_flight = false;
-    return 0;
-}
+int rg_tick_wait(rg_tick_t *k) { return recording_wait(k); }
 
 static rg::TimerParams timer_params(rg_table *t);
 static rg::HealthParams health_params(rg_table *t);
 
 /* the device-resident tick: see include/raftgpu.h */
-struct rg_tick2 {
-    rg_table *t = nullptr;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    uint64_t config_gen = 0;
-    bool in_flight = false;
-};
-
-static void tick2_release(struct rg_tick2 *k)
-{
-    if (k->exec) (void)hipGraphExecDestroy(k->exec);
-    if (k->graph) (void)hipGraphDestroy(k->graph);
-    k->exec = nullptr; k->graph = nullptr;
-    k->t = nullptr;
-}
-
-int rg_tick2_destroy(rg_tick2_t *k)
-{
-    if (!k) return 0;
-    if (rg_table *t = k->t) {
-        (void)hipSetDevice(t->device);
-        if (t->stream) (void)hipStreamSynchronize(t->stream);
-        t->ticks2.erase(std::remove(t->ticks2.begin(), t->ticks2.end(), k), t->ticks2.end());
-        tick2_release(k);
-    }
-    delete k;
-    return 0;
-}
+int rg_tick2_destroy(rg_tick2_t *k) { return recording_destroy(k, &rg_table::ticks2); }
 
 // the device's address of memory the caller says is device-visible: page-locked host memory is mapped, device memory is what it is; pageable host
 // memory (which a kernel would fault on) is refused where the runtime can tell
@@ -905,13 +981,8 @@ static int tick2_create(rg_table_t *t, const rg_tick2_io_t *io, const rg_tick2_r
         if (rows->capacity == 0 || rows->capacity > t->G) return fail(t, -1, "%s: a capacity of %u rows for %u groups (1 .. groups)", who, rows->capacity, t->G);
     }
     const uint32_t R = rows ? rows->capacity : t->G;        // rows the per-row columns are sized for
-    rg_batch_t wide{};
-    wide.rounds = io->rounds; wide.count = R; wide.gid = rows ? rows->gid : nullptr; wide.head = io->head;
-    wide.ab = wide.cd = reinterpret_cast<const rg_ev_pair_t *>(io->abcd);
-    wide.entry_terms = reinterpret_cast<const int64_t *>(io->entry_terms); wide.entry_count = io->entry_capacity;
-    rg_reply_t dummy_r; rg_logfx_t dummy_l; rg_persist_t dummy_p;
-    const rg_outcome_t shape{&dummy_r, &dummy_l, &dummy_p};
-    if (int rc = check_batch(t, &wide, &shape, false, deep)) return rc;
+    const Shape shape{io->rounds, R, rows ? rows->gid : nullptr, io->entry_capacity, io->entry_terms != nullptr};
+    if (int rc = check_shape(t, shape, false, deep)) return rc;
     if (bind(t)) return -2;
     const auto visible = [t](const void *p, const char *what, void **out) { return device_visible(t, "rg_tick2_create", p, what, out); };      // (whichever constructor: the refusals have always said rg_tick2_create)
     void *d_head, *d_abcd, *d_terms, *d_now, *d_hb, *d_fl, *d_row, *d_per, *d_egid, *d_eep, *d_ecnt, *d_sh, *d_ss, *d_ready, *d_gid = nullptr, *d_cnt = nullptr, *d_depth = nullptr;
@@ -926,7 +997,7 @@ static int tick2_create(rg_table_t *t, const rg_tick2_io_t *io, const rg_tick2_r
     k->t = t;
     k->config_gen = t->config_gen;
     // the decisions: rg_submit32c / rg_submit32c_sparse on device-visible rows
-    rg::StepParams sp = step_params(t, &wide);
+    rg::StepParams sp = step_params(t, shape);
     sp.gid = (const uint32_t *)d_gid;
     sp.head = (const rg_ev_head_t *)d_head; sp.abcd32 = (const rg::I32x4 *)d_abcd;
     sp.entry_terms32 = io->entry_capacity ? (const int32_t *)d_terms : nullptr;
@@ -978,13 +1049,7 @@ static int tick2_create(rg_table_t *t, const rg_tick2_io_t *io, const rg_tick2_r
             if (e == hipSuccess && io->ready) e = rg::launch_ready(rp, 0, io->critical_point, io->cool_down_ms, (uint8_t *)d_ready, s);
         }
     }
-    hipGraph_t g = nullptr;
-    const hipError_t e2 = hipStreamEndCapture(s, &g);           // (always: an open capture would poison the stream)
-    k->graph = g;
-    if (e == hipSuccess) e = e2;
-    if (e == hipSuccess) e = hipGraphInstantiate(&k->exec, k->graph, nullptr, nullptr, 0);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
+    if ((e = recording_finish(k, e)) != hipSuccess) {
         rg_tick2_destroy(k);
         return fail(t, -2, "%s: %s", who, hipGetErrorString(e));
     }
@@ -1014,36 +1079,26 @@ int rg_tick2_create_sparse_rounds(rg_table_t *t, const rg_tick2_io_t *io, const 
 
 int rg_tick2_launch(rg_tick2_t *k)
 {
-    if (!k || !k->t) return -1;
+    if (int rc = recording_bind(k, "rg_tick2_launch", "rg_tick2_create")) return rc;
     rg_table *t = k->t;
-    if (k->config_gen != t->config_gen)
-        return fail(t, -1, "rg_tick2_launch: the table's options or index bases changed after rg_tick2_create (they are part of the recording): create the tick again");
-    if (bind(t)) return -2;
     HIP_TRY(t, hipGraphLaunch(k->exec, t->stream));             // (a launch behind one in flight is ordered after it on the stream: include/raftgpu.h)
     k->in_flight = true;
     return 0;
 }
 
-int rg_tick2_wait(rg_tick2_t *k)
-{
-    if (!k || !k->t) return -1;
-    rg_table *t = k->t;
-    HIP_TRY(t, hipSetDevice(t->device));
-    HIP_TRY(t, hipStreamSynchronize(t->stream));
-    k->in_flight = false;
-    return 0;
-}
+int rg_tick2_wait(rg_tick2_t *k) { return recording_wait(k); }
 
 /* ---- assembling a batch on the device (rg_assemble32; kernels: rg_assemble.hpp) ------------------------------------------------------ */
 struct rg_assembler {
     rg_table *t = nullptr;
     uint32_t max_events = 0, max_expired = 0;
     rg::AsmParams sc{};                             // the scratch pointers and their capacities; the rest is filled per run
-    Staging in_words, in_gid, in_head, in_abcd, ex_gid, ex_epoch;                       // RG_MEM_HOST: the sources ...
-    Staging out_gid, out_words, out_head, out_abcd, out_origin, out_deferred;           // ... and the batch
-    bool ran = false;                               // rg_route32 routes the last run: its shape, and the scratch of the route's lists
+    enum { IN_WORDS, IN_GID, IN_HEAD, IN_ABCD, EX_GID, EX_EPOCH,                        // RG_MEM_HOST: the sources ...
+           OUT_GID, OUT_WORDS, OUT_HEAD, OUT_ABCD, OUT_ORIGIN, OUT_DEFERRED,            // ... and the batch
+           ROUTE_PC, ROUTE_AC, ROUTE_SC, AS_COLUMNS };                                  // RG_MEM_DEVICE routes: the scratch of the route's lists
+    Staging as[AS_COLUMNS];
+    bool ran = false;                               // rg_route32 routes the last run: its shape
     uint32_t last_C = 0, last_D = 0, last_in_cap = 0, last_ex_cap = 0;
-    Staging route_pc, route_ac, route_sc;
     enum { RT_GID, RT_WORDS, RT_ORIGIN, RT_ROW, RT_PERSIST, RT_SEND, RT_CELL, RT_OROW, RT_OPERSIST, RT_XCELL, RT_XROW, RT_XPERSIST, RT_PLIST, RT_ALIST, RT_SLIST, RT_SOFF,
            RT_COUNTS, RT_PC, RT_AC, RT_SC, RT_COLUMNS };
     Staging rt[RT_COLUMNS];                         // RG_MEM_HOST: the columns of rg_decided_t and rg_routed_t, and the lists' count arrays
@@ -1051,12 +1106,10 @@ struct rg_assembler {
 
 static void assembler_release(struct rg_assembler *a)
 {
-    void *cols[] = {a->sc.cnt, a->sc.bitmap, a->sc.rowof, a->sc.wordoff, a->sc.rowcnt, a->sc.segoff, a->sc.seg, a->sc.flag, a->sc.dcounts, a->sc.big, a->sc.scalars,
-                    a->in_words.ptr, a->in_gid.ptr, a->in_head.ptr, a->in_abcd.ptr, a->ex_gid.ptr, a->ex_epoch.ptr,
-                    a->out_gid.ptr, a->out_words.ptr, a->out_head.ptr, a->out_abcd.ptr, a->out_origin.ptr, a->out_deferred.ptr,
-                    a->route_pc.ptr, a->route_ac.ptr, a->route_sc.ptr};
+    void *cols[] = {a->sc.cnt, a->sc.bitmap, a->sc.rowof, a->sc.wordoff, a->sc.rowcnt, a->sc.segoff, a->sc.seg, a->sc.flag, a->sc.dcounts, a->sc.big, a->sc.scalars};
     for (void *c : cols) if (c) (void)hipFree(c);
-    for (Staging &c : a->rt) if (c.ptr) (void)hipFree(c.ptr);
+    release(a->as, rg_assembler::AS_COLUMNS);
+    release(a->rt, rg_assembler::RT_COLUMNS);
     *a = rg_assembler{};
 }
 
@@ -1154,29 +1207,18 @@ int rg_assemble32(rg_assembler_t *a, const rg_arrivals_t *in, const rg_assembled
     // host memory: stage the sources in (as much of them as this run reads), run, bring back what the run wrote — rows 0 .. n - 1 of rounds 0 .. R - 1 — and nothing else
     const uint32_t m = *in->count < in->capacity ? *in->count : in->capacity;
     const uint32_t e = !expired || *in->expired_count == 0xFFFFFFFFu ? 0u : (*in->expired_count < ex_cap ? *in->expired_count : ex_cap);
-    if (reserve(t, a->in_words, 2 * sizeof(uint32_t)) || reserve(t, a->in_gid, (size_t)m * sizeof(uint32_t)) || reserve(t, a->in_head, (size_t)m * sizeof(rg_ev_head_t)) ||
-        reserve(t, a->in_abcd, (size_t)m * sizeof(rg_ev_quad32_t)) || reserve(t, a->ex_gid, (size_t)e * sizeof(uint32_t)) || reserve(t, a->ex_epoch, (size_t)e * sizeof(uint32_t)) ||
-        reserve(t, a->out_gid, (size_t)C * sizeof(uint32_t)) || reserve(t, a->out_words, 6 * sizeof(uint32_t)) || reserve(t, a->out_head, cells * sizeof(rg_ev_head_t)) ||
-        reserve(t, a->out_abcd, cells * sizeof(rg_ev_quad32_t)) || reserve(t, a->out_origin, cells * sizeof(uint32_t)) ||
-        reserve(t, a->out_deferred, (size_t)out->deferred_capacity * sizeof(uint32_t)))
-        return -2;
+    typedef rg_assembler A;
     const uint32_t words_in[2] = {*in->count, expired ? *in->expired_count : 0u};
-    HIP_TRY(t, hipMemcpyAsync(a->in_words.ptr, words_in, sizeof words_in, hipMemcpyHostToDevice, s));
-    if (m) {
-        HIP_TRY(t, hipMemcpyAsync(a->in_gid.ptr, in->gid, (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        HIP_TRY(t, hipMemcpyAsync(a->in_head.ptr, in->head, (size_t)m * sizeof(rg_ev_head_t), hipMemcpyHostToDevice, s));
-        HIP_TRY(t, hipMemcpyAsync(a->in_abcd.ptr, in->abcd, (size_t)m * sizeof(rg_ev_quad32_t), hipMemcpyHostToDevice, s));
-    }
-    if (e) {
-        HIP_TRY(t, hipMemcpyAsync(a->ex_gid.ptr, in->expired_gid, (size_t)e * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        HIP_TRY(t, hipMemcpyAsync(a->ex_epoch.ptr, in->expired_epoch, (size_t)e * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    }
-    uint32_t *ow = (uint32_t *)a->out_words.ptr;                       // {n, R, stats[4]}
-    p.in_count = (const uint32_t *)a->in_words.ptr; p.in_gid = (const uint32_t *)a->in_gid.ptr;
-    p.in_head = (const rg::U32x2 *)a->in_head.ptr; p.in_abcd = (const rg::I32x4 *)a->in_abcd.ptr;
-    p.ex_gid = (const uint32_t *)a->ex_gid.ptr; p.ex_epoch = (const uint32_t *)a->ex_epoch.ptr; p.ex_count = expired ? (const uint32_t *)a->in_words.ptr + 1 : nullptr;
-    p.gid = (uint32_t *)a->out_gid.ptr; p.count = ow; p.rounds = ow + 1; p.stats = ow + 2;
-    p.head = (rg::U32x2 *)a->out_head.ptr; p.abcd = (rg::I32x4 *)a->out_abcd.ptr; p.origin = (uint32_t *)a->out_origin.ptr; p.deferred = (uint32_t *)a->out_deferred.ptr;
+    uint32_t *ow = nullptr;                                            // {n, R, stats[4]}
+    if (stage_in(t, a->as[A::IN_WORDS], words_in, 2, s, &p.in_count) || stage_in(t, a->as[A::IN_GID], in->gid, m, s, &p.in_gid) ||
+        stage_in(t, a->as[A::IN_HEAD], in->head, m, s, &p.in_head) || stage_in(t, a->as[A::IN_ABCD], in->abcd, m, s, &p.in_abcd) ||
+        stage_in(t, a->as[A::EX_GID], in->expired_gid, e, s, &p.ex_gid) || stage_in(t, a->as[A::EX_EPOCH], in->expired_epoch, e, s, &p.ex_epoch) ||
+        stage_out(t, a->as[A::OUT_GID], C, &p.gid) || stage_out(t, a->as[A::OUT_WORDS], 6, &ow) || stage_out(t, a->as[A::OUT_HEAD], cells, &p.head) ||
+        stage_out(t, a->as[A::OUT_ABCD], cells, &p.abcd) || stage_out(t, a->as[A::OUT_ORIGIN], cells, &p.origin) ||
+        stage_out(t, a->as[A::OUT_DEFERRED], out->deferred_capacity, &p.deferred))
+        return -2;
+    p.ex_count = expired ? p.in_count + 1 : nullptr;
+    p.count = ow; p.rounds = ow + 1; p.stats = ow + 2;
     HIP_TRY(t, rg::launch_assemble(p, s));
     a->ran = true; a->last_C = C; a->last_D = D; a->last_in_cap = in->capacity; a->last_ex_cap = ex_cap;
     uint32_t back[6] = {};
@@ -1185,17 +1227,15 @@ int rg_assemble32(rg_assembler_t *a, const rg_arrivals_t *in, const rg_assembled
     const uint32_t n = back[0], R = back[1];
     *out->count = n; *out->rounds = R;
     memcpy(out->stats, back + 2, 4 * sizeof(uint32_t));
-    if (n) {
-        HIP_TRY(t, hipMemcpyAsync(out->gid, a->out_gid.ptr, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        for (uint32_t r = 0; r < R; r++) {
-            const size_t at = (size_t)r * C;
-            HIP_TRY(t, hipMemcpyAsync(out->head + at, (rg_ev_head_t *)a->out_head.ptr + at, (size_t)n * sizeof(rg_ev_head_t), hipMemcpyDeviceToHost, s));
-            HIP_TRY(t, hipMemcpyAsync(out->abcd + at, (rg_ev_quad32_t *)a->out_abcd.ptr + at, (size_t)n * sizeof(rg_ev_quad32_t), hipMemcpyDeviceToHost, s));
-            HIP_TRY(t, hipMemcpyAsync(out->origin + at, (uint32_t *)a->out_origin.ptr + at, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        }
+    HIP_TRY(t, col_down(a->as[A::OUT_GID], out->gid, 0, n, s));
+    for (uint32_t r = 0; r < R; r++) {
+        const size_t at = (size_t)r * C;
+        HIP_TRY(t, col_down(a->as[A::OUT_HEAD], out->head, at, n, s));
+        HIP_TRY(t, col_down(a->as[A::OUT_ABCD], out->abcd, at, n, s));
+        HIP_TRY(t, col_down(a->as[A::OUT_ORIGIN], out->origin, at, n, s));
     }
     const uint32_t kept = back[3] < out->deferred_capacity ? back[3] : out->deferred_capacity;
-    if (kept) HIP_TRY(t, hipMemcpyAsync(out->deferred, a->out_deferred.ptr, (size_t)kept * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(t, col_down(a->as[A::OUT_DEFERRED], out->deferred, 0, kept, s));
     HIP_TRY(t, hipStreamSynchronize(s));
     return 0;
 }
@@ -1236,6 +1276,7 @@ int rg_route32(rg_assembler_t *a, const rg_decided_t *in, const rg_routed_t *out
     p.C = C; p.D = D; p.F = F; p.in_cap = in_cap; p.ex_cap = ex_cap; p.last = a->sc.scalars + rg::ASM_LAST; p.span = rg::route_span(C, D, F); p.bpr = (uint32_t)((C + 4ull * p.span - 1) / (4ull * p.span));
     p.persist_cap = out->persist_capacity; p.attention_cap = out->attention_capacity; p.send_cap = sends ? out->send_capacity : 0u;
     const size_t W = (size_t)D * p.bpr * 4, Ws = (size_t)F * p.bpr * 4;
+    typedef rg_assembler A;
     if (memspace == RG_MEM_DEVICE) {
         void *v[24] = {};
         const struct { const void *ptr; const char *what; } cols[] = {
@@ -1246,14 +1287,12 @@ int rg_route32(rg_assembler_t *a, const rg_decided_t *in, const rg_routed_t *out
         int k = 0;
         for (const auto &c : cols) if (int rc = device_visible(t, who, c.ptr, c.what, &v[k++])) return rc;
         if (bind(t)) return -2;
-        if (reserve(t, a->route_pc, (W + 1) * sizeof(uint32_t)) || reserve(t, a->route_ac, (W + 1) * sizeof(uint32_t)) || (sends && reserve(t, a->route_sc, (Ws + 1) * sizeof(uint32_t))))
-            return -2;
+        if (stage_out(t, a->as[A::ROUTE_PC], W + 1, &p.pc) || stage_out(t, a->as[A::ROUTE_AC], W + 1, &p.ac) || (sends && stage_out(t, a->as[A::ROUTE_SC], Ws + 1, &p.sc))) return -2;
         p.gid = (const uint32_t *)v[0]; p.count = (const uint32_t *)v[1]; p.rounds = (const uint32_t *)v[2]; p.origin = (const uint32_t *)v[3];
         p.row = (const rg::I32x4 *)v[4]; p.persist32 = (const rg::I32x4 *)v[5]; p.send = sends ? (const rg_send_t *)v[7] : nullptr;
         p.cell = (uint32_t *)v[8]; p.out_row = (rg::I32x4 *)v[9]; p.out_persist = (rg::I32x4 *)v[10];
         p.ex_cell = (uint32_t *)v[11]; p.ex_row = (rg::I32x4 *)v[12]; p.ex_persist = (rg::I32x4 *)v[13];
         p.persist_list = (rg::U32x2 *)v[14]; p.attention = (rg::U32x2 *)v[15]; p.send_list = (rg::U32x2 *)v[16]; p.send_offset = (uint32_t *)v[17]; p.counts = (uint32_t *)v[18];
-        p.pc = (uint32_t *)a->route_pc.ptr; p.ac = (uint32_t *)a->route_ac.ptr; p.sc = (uint32_t *)a->route_sc.ptr;
         HIP_TRY(t, rg::launch_route(p, t->stream));
         return 0;
     }
@@ -1267,56 +1306,52 @@ int rg_route32(rg_assembler_t *a, const rg_decided_t *in, const rg_routed_t *out
     const uint32_t e = expired ? (last[0] < ex_cap ? last[0] : ex_cap) : 0u, m = last[1] < in_cap ? last[1] : in_cap;
     const uint32_t n = *in->count < C ? *in->count : C, R = *in->rounds < 1 ? 1u : (*in->rounds < D ? *in->rounds : D);
     const size_t cells = (size_t)C * D;
-    enum { GID = rg_assembler::RT_GID, WORDS, ORIGIN, ROW, PERSIST, SEND, CELL, OROW, OPERSIST, XCELL, XROW, XPERSIST, PLIST, ALIST, SLIST, SOFF, COUNTS, PC, AC, SC, COLUMNS };
-    static_assert(COLUMNS == rg_assembler::RT_COLUMNS, "one staging buffer per column");
-    const size_t bytes[COLUMNS] = {(size_t)C * 4, 8, cells * 4, cells * 16, cells * 16, sends ? (size_t)F * C * sizeof(rg_send_t) : 0, (size_t)m * 4, (size_t)m * 16, (size_t)m * 16,
-                              (size_t)e * 4, (size_t)e * 16, (size_t)e * 16, (size_t)p.persist_cap * 8, (size_t)p.attention_cap * 8, (size_t)p.send_cap * 8, ((size_t)F + 1) * 4, 16,
-                              (W + 1) * 4, (W + 1) * 4, (Ws + 1) * 4};
-    for (int k = 0; k < COLUMNS; k++) if (reserve(t, a->rt[k], bytes[k] ? bytes[k] : 16)) return -2;
-    auto dev = [&](int k) { return (char *)a->rt[k].ptr; };
-    auto up = [&](int k, const void *src, size_t at, size_t len) { return len ? hipMemcpyAsync(dev(k) + at, (const char *)src + at, len, hipMemcpyHostToDevice, s) : hipSuccess; };
-    auto down = [&](int k, void *dst, size_t at, size_t len) { return len ? hipMemcpyAsync((char *)dst + at, dev(k) + at, len, hipMemcpyDeviceToHost, s) : hipSuccess; };
+    Staging *rt = a->rt;
     const uint32_t words[2] = {n, R};
-    HIP_TRY(t, hipMemcpyAsync(dev(WORDS), words, sizeof words, hipMemcpyHostToDevice, s));
-    HIP_TRY(t, up(GID, in->gid, 0, (size_t)n * 4));
+    // every column gets a buffer, an absent or empty one 16 bytes
+    auto col = [&](int k, size_t len, auto **dev) { return stage_out(t, rt[k], len ? len : 16 / sizeof(**dev), dev); };
+    if (stage_in(t, rt[A::RT_WORDS], words, 2, s, &p.count) || col(A::RT_GID, C, &p.gid) || col(A::RT_ORIGIN, cells, &p.origin) || col(A::RT_ROW, cells, &p.row) ||
+        col(A::RT_PERSIST, cells, &p.persist32) || col(A::RT_SEND, sends ? (size_t)F * C : 0, &p.send) || col(A::RT_CELL, m, &p.cell) || col(A::RT_OROW, m, &p.out_row) ||
+        col(A::RT_OPERSIST, m, &p.out_persist) || col(A::RT_XCELL, e, &p.ex_cell) || col(A::RT_XROW, e, &p.ex_row) || col(A::RT_XPERSIST, e, &p.ex_persist) ||
+        col(A::RT_PLIST, p.persist_cap, &p.persist_list) || col(A::RT_ALIST, p.attention_cap, &p.attention) || col(A::RT_SLIST, p.send_cap, &p.send_list) ||
+        col(A::RT_SOFF, (size_t)F + 1, &p.send_offset) || col(A::RT_COUNTS, 4, &p.counts) || col(A::RT_PC, W + 1, &p.pc) || col(A::RT_AC, W + 1, &p.ac) ||
+        col(A::RT_SC, Ws + 1, &p.sc))
+        return -2;
+    p.rounds = p.count + 1;
+    if (!sends) p.send = nullptr;
+    if (!expired) p.ex_cell = nullptr, p.ex_row = p.ex_persist = nullptr;
+    HIP_TRY(t, col_up(rt[A::RT_GID], in->gid, 0, n, s));
     for (uint32_t r = 0; r < R; r++) {
         const size_t at = (size_t)r * C;
-        HIP_TRY(t, up(ORIGIN, in->origin, at * 4, (size_t)n * 4));
-        HIP_TRY(t, up(ROW, in->row, at * 16, (size_t)n * 16));
-        HIP_TRY(t, up(PERSIST, in->persist32, at * 16, (size_t)n * 16));
+        HIP_TRY(t, col_up(rt[A::RT_ORIGIN], in->origin, at, n, s));
+        HIP_TRY(t, col_up(rt[A::RT_ROW], in->row, at, n, s));
+        HIP_TRY(t, col_up(rt[A::RT_PERSIST], in->persist32, at, n, s));
     }
-    for (uint32_t j = 0; sends && j < F; j++) HIP_TRY(t, up(SEND, in->send, (size_t)j * C * sizeof(rg_send_t), (size_t)n * sizeof(rg_send_t)));
-    HIP_TRY(t, up(OROW, out->row, 0, (size_t)m * 16));
-    HIP_TRY(t, up(OPERSIST, out->persist32, 0, (size_t)m * 16));
+    for (uint32_t j = 0; sends && j < F; j++) HIP_TRY(t, col_up(rt[A::RT_SEND], in->send, (size_t)j * C, n, s));
+    HIP_TRY(t, col_up(rt[A::RT_OROW], out->row, 0, m, s));
+    HIP_TRY(t, col_up(rt[A::RT_OPERSIST], out->persist32, 0, m, s));
     if (expired) {
-        HIP_TRY(t, up(XROW, out->expired_row, 0, (size_t)e * 16));
-        HIP_TRY(t, up(XPERSIST, out->expired_persist32, 0, (size_t)e * 16));
+        HIP_TRY(t, col_up(rt[A::RT_XROW], out->expired_row, 0, e, s));
+        HIP_TRY(t, col_up(rt[A::RT_XPERSIST], out->expired_persist32, 0, e, s));
     }
-    p.count = (const uint32_t *)dev(WORDS); p.rounds = p.count + 1; p.gid = (const uint32_t *)dev(GID); p.origin = (const uint32_t *)dev(ORIGIN);
-    p.row = (const rg::I32x4 *)dev(ROW); p.persist32 = (const rg::I32x4 *)dev(PERSIST); p.send = sends ? (const rg_send_t *)dev(SEND) : nullptr;
-    p.cell = (uint32_t *)dev(CELL); p.out_row = (rg::I32x4 *)dev(OROW); p.out_persist = (rg::I32x4 *)dev(OPERSIST);
-    if (expired) { p.ex_cell = (uint32_t *)dev(XCELL); p.ex_row = (rg::I32x4 *)dev(XROW); p.ex_persist = (rg::I32x4 *)dev(XPERSIST); }
-    p.persist_list = (rg::U32x2 *)dev(PLIST); p.attention = (rg::U32x2 *)dev(ALIST); p.send_list = (rg::U32x2 *)dev(SLIST);
-    p.send_offset = (uint32_t *)dev(SOFF); p.counts = (uint32_t *)dev(COUNTS);
-    p.pc = (uint32_t *)dev(PC); p.ac = (uint32_t *)dev(AC); p.sc = (uint32_t *)dev(SC);
     HIP_TRY(t, rg::launch_route(p, s));
     uint32_t counts[4] = {};
-    HIP_TRY(t, hipMemcpyAsync(counts, dev(COUNTS), sizeof counts, hipMemcpyDeviceToHost, s));
+    HIP_TRY(t, col_down(rt[A::RT_COUNTS], counts, 0, 4, s));
     HIP_TRY(t, hipStreamSynchronize(s));
     memcpy(out->counts, counts, sizeof counts);
-    HIP_TRY(t, down(CELL, out->cell, 0, (size_t)m * 4));
-    HIP_TRY(t, down(OROW, out->row, 0, (size_t)m * 16));
-    HIP_TRY(t, down(OPERSIST, out->persist32, 0, (size_t)m * 16));
+    HIP_TRY(t, col_down(rt[A::RT_CELL], out->cell, 0, m, s));
+    HIP_TRY(t, col_down(rt[A::RT_OROW], out->row, 0, m, s));
+    HIP_TRY(t, col_down(rt[A::RT_OPERSIST], out->persist32, 0, m, s));
     if (expired) {
-        HIP_TRY(t, down(XCELL, out->expired_cell, 0, (size_t)e * 4));
-        HIP_TRY(t, down(XROW, out->expired_row, 0, (size_t)e * 16));
-        HIP_TRY(t, down(XPERSIST, out->expired_persist32, 0, (size_t)e * 16));
+        HIP_TRY(t, col_down(rt[A::RT_XCELL], out->expired_cell, 0, e, s));
+        HIP_TRY(t, col_down(rt[A::RT_XROW], out->expired_row, 0, e, s));
+        HIP_TRY(t, col_down(rt[A::RT_XPERSIST], out->expired_persist32, 0, e, s));
     }
-    HIP_TRY(t, down(PLIST, out->persist_list, 0, (size_t)(counts[0] < p.persist_cap ? counts[0] : p.persist_cap) * 8));
-    HIP_TRY(t, down(ALIST, out->attention, 0, (size_t)(counts[1] < p.attention_cap ? counts[1] : p.attention_cap) * 8));
+    HIP_TRY(t, col_down(rt[A::RT_PLIST], out->persist_list, 0, counts[0] < p.persist_cap ? counts[0] : p.persist_cap, s));
+    HIP_TRY(t, col_down(rt[A::RT_ALIST], out->attention, 0, counts[1] < p.attention_cap ? counts[1] : p.attention_cap, s));
     if (sends) {
-        HIP_TRY(t, down(SLIST, out->send_list, 0, (size_t)(counts[2] < p.send_cap ? counts[2] : p.send_cap) * 8));
-        HIP_TRY(t, down(SOFF, out->send_offset, 0, ((size_t)F + 1) * 4));
+        HIP_TRY(t, col_down(rt[A::RT_SLIST], out->send_list, 0, counts[2] < p.send_cap ? counts[2] : p.send_cap, s));
+        HIP_TRY(t, col_down(rt[A::RT_SOFF], out->send_offset, 0, (size_t)F + 1, s));
     }
     HIP_TRY(t, hipStreamSynchronize(s));
     return 0;
@@ -1338,7 +1373,7 @@ int rg_submit(rg_table_t *t, const rg_batch_t *in, const rg_outcome_t *out, int 
     const bool sparse = in->gid != nullptr;
 
     const size_t rows = (size_t)in->rounds * in->count;
-    rg::StepParams p = step_params(t, in);
+    rg::StepParams p = step_params(t, shape_of(in));
 
     if (memspace == RG_MEM_DEVICE) {
         p.gid = in->gid; p.head = in->head;
@@ -1350,38 +1385,51 @@ int rg_submit(rg_table_t *t, const rg_batch_t *in, const rg_outcome_t *out, int 
     if (memspace != RG_MEM_HOST) return fail(t, -1, "rg_submit: unknown memspace %d", memspace);
 
     hipStream_t s = t->stream;
-    if (reserve(t, t->st_head, rows * sizeof(rg_ev_head_t)) || reserve(t, t->st_ab, rows * sizeof(I64x2)) ||
-        reserve(t, t->st_cd, rows * sizeof(I64x2)) || reserve(t, t->st_reply, rows * sizeof(rg_reply_t)) ||
-        reserve(t, t->st_logfx, rows * sizeof(I64x2)) || reserve(t, t->st_persist, rows * sizeof(rg_persist_t)))
-        return -2;
-    HIP_TRY(t, hipMemcpyAsync(t->st_head.ptr, in->head, rows * sizeof(rg_ev_head_t), hipMemcpyHostToDevice, s));
-    HIP_TRY(t, hipMemcpyAsync(t->st_ab.ptr, in->ab, rows * sizeof(I64x2), hipMemcpyHostToDevice, s));
-    HIP_TRY(t, hipMemcpyAsync(t->st_cd.ptr, in->cd, rows * sizeof(I64x2), hipMemcpyHostToDevice, s));
-    p.head = (const rg_ev_head_t *)t->st_head.ptr;
-    p.ab = (const I64x2 *)t->st_ab.ptr; p.cd = (const I64x2 *)t->st_cd.ptr;
-    if (sparse) {
-        if (reserve(t, t->st_gid, in->count * sizeof(uint32_t))) return -2;
-        HIP_TRY(t, hipMemcpyAsync(t->st_gid.ptr, in->gid, in->count * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        p.gid = (const uint32_t *)t->st_gid.ptr;
-    }
-    if (in->hint) {
-        if (reserve(t, t->st_hint, rows * sizeof(I64x2))) return -2;
-        HIP_TRY(t, hipMemcpyAsync(t->st_hint.ptr, in->hint, rows * sizeof(I64x2), hipMemcpyHostToDevice, s));
-        p.hint = (const I64x2 *)t->st_hint.ptr;
-    }
-    if (in->entry_count) {
-        if (reserve(t, t->st_terms, in->entry_count * sizeof(int64_t))) return -2;
-        HIP_TRY(t, hipMemcpyAsync(t->st_terms.ptr, in->entry_terms, in->entry_count * sizeof(int64_t), hipMemcpyHostToDevice, s));
-        p.entry_terms = (const int64_t *)t->st_terms.ptr;
-    }
-    p.reply = (rg_reply_t *)t->st_reply.ptr; p.logfx = (I64x2 *)t->st_logfx.ptr; p.persist = (rg_persist_t *)t->st_persist.ptr;
+    if (int rc = outcome_wide(t, t->st, rows, p)) return rc;
+    if (int rc = upload_wide(t, t->st, in, s, p)) return rc;
     // conditional outputs: rows the kernel does not write come back zeroed (they are only valid when flagged)
-    HIP_TRY(t, hipMemsetAsync(t->st_logfx.ptr, 0, rows * sizeof(I64x2), s));
-    HIP_TRY(t, hipMemsetAsync(t->st_persist.ptr, 0, rows * sizeof(rg_persist_t), s));
+    HIP_TRY(t, hipMemsetAsync(p.logfx, 0, rows * sizeof(I64x2), s));
+    HIP_TRY(t, hipMemsetAsync(p.persist, 0, rows * sizeof(rg_persist_t), s));
     if (int rc = launch(t, p, sparse)) return rc;
-    HIP_TRY(t, hipMemcpyAsync(out->reply, t->st_reply.ptr, rows * sizeof(rg_reply_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(t, hipMemcpyAsync(out->logfx, t->st_logfx.ptr, rows * sizeof(I64x2), hipMemcpyDeviceToHost, s));
-    HIP_TRY(t, hipMemcpyAsync(out->persist, t->st_persist.ptr, rows * sizeof(rg_persist_t), hipMemcpyDeviceToHost, s));
+    if (int rc = download_wide(t, t->st, *out, rows, s)) return rc;
+    HIP_TRY(t, hipStreamSynchronize(s));
+    return 0;
+}
+
+/* Compact rows decided into the wide outcome columns w (rg_submit32), into the compact outcome rows c32 (rg_submit32c*), or into c32 with w as its overflow
+ * columns; either may be nullptr. The callers have checked their arguments and the shape. */
+static int submit_compact(rg_table *t, const rg_batch32_t *in, const rg_outcome_t *w, const rg_outcome32_t *c32, int memspace, const char *who)
+{
+    if (in->count == 0) return 0;
+    if (bind(t)) return -2;
+    const bool sparse = in->gid != nullptr;
+    const size_t rows = (size_t)in->rounds * in->count;
+    rg::StepParams p = step_params(t, shape_of(in));
+    if (memspace == RG_MEM_DEVICE) {
+        p.gid = in->gid; p.head = in->head; p.abcd32 = (const rg::I32x4 *)in->abcd;
+        p.entry_terms32 = in->entry_count ? in->entry_terms : nullptr;
+        if (c32) { p.out32 = (rg::I32x4 *)c32->row; p.persist32 = (rg::I32x4 *)c32->persist; }
+        if (w) { p.reply = w->reply; p.logfx = (I64x2 *)w->logfx; p.persist = w->persist; }
+        return launch(t, p, sparse);
+    }
+    if (memspace != RG_MEM_HOST) return fail(t, -1, "%s: unknown memspace %d", who, memspace);
+    hipStream_t s = t->stream;
+    BatchCols &c = t->st;
+    if (c32 && (stage_out(t, c[C_OUT32], rows, &p.out32) || stage_out(t, c[C_PERSIST32], rows, &p.persist32))) return -2;
+    if (w)
+        if (int rc = outcome_wide(t, c, rows, p)) return rc;
+    if (int rc = upload_compact(t, c, in, s, p)) return rc;
+    // conditional rows come back zeroed, as rg_submit's; as overflow columns the reply rows are conditional too
+    if (c32) HIP_TRY(t, hipMemsetAsync(p.persist32, 0, rows * sizeof(rg_persist32_t), s));
+    if (c32 && w) HIP_TRY(t, hipMemsetAsync(p.reply, 0, rows * sizeof(rg_reply_t), s));
+    if (w) {
+        HIP_TRY(t, hipMemsetAsync(p.logfx, 0, rows * sizeof(I64x2), s));
+        HIP_TRY(t, hipMemsetAsync(p.persist, 0, rows * sizeof(rg_persist_t), s));
+    }
+    if (int rc = launch(t, p, sparse)) return rc;
+    if (c32 && (stage_back(t, c[C_OUT32], c32->row, rows, s) || stage_back(t, c[C_PERSIST32], c32->persist, rows, s))) return -2;
+    if (w)
+        if (int rc = download_wide(t, c, *w, rows, s)) return rc;
     HIP_TRY(t, hipStreamSynchronize(s));
     return 0;
 }
@@ -1393,50 +1441,9 @@ int rg_submit32(rg_table_t *t, const rg_batch32_t *in, const rg_outcome_t *out, 
     if (int rc = compact_ok(t, "rg_submit32")) return rc;
     if (!in || !out) return fail(t, -1, "rg_submit32: NULL batch or outcome");
     if (!in->head || !in->abcd) return fail(t, -1, "rg_submit32: head and abcd are required");
-    rg_batch_t wide{};                              // the same shape rules as every other submission (rounds, count, gid list, entry bound)
-    wide.rounds = in->rounds; wide.count = in->count; wide.gid = in->gid; wide.head = in->head;
-    wide.ab = wide.cd = reinterpret_cast<const rg_ev_pair_t *>(in->abcd);      // presence only: check_batch does not read event fields
-    wide.entry_terms = reinterpret_cast<const int64_t *>(in->entry_terms); wide.entry_count = in->entry_count;
-    if (int rc = check_batch(t, &wide, out, memspace == RG_MEM_HOST)) return rc;
-    if (in->count == 0) return 0;
-    if (bind(t)) return -2;
-    const bool sparse = in->gid != nullptr;
-    const size_t rows = (size_t)in->rounds * in->count;
-    rg::StepParams p = step_params(t, &wide);
-    if (memspace == RG_MEM_DEVICE) {
-        p.gid = in->gid; p.head = in->head; p.abcd32 = (const rg::I32x4 *)in->abcd;
-        p.entry_terms32 = in->entry_count ? in->entry_terms : nullptr;
-        p.reply = out->reply; p.logfx = (I64x2 *)out->logfx; p.persist = out->persist;
-        return launch(t, p, sparse);
-    }
-    if (memspace != RG_MEM_HOST) return fail(t, -1, "rg_submit32: unknown memspace %d", memspace);
-    hipStream_t s = t->stream;
-    if (reserve(t, t->st_head, rows * sizeof(rg_ev_head_t)) || reserve(t, t->st_abcd32, rows * sizeof(rg_ev_quad32_t)) ||
-        reserve(t, t->st_reply, rows * sizeof(rg_reply_t)) || reserve(t, t->st_logfx, rows * sizeof(I64x2)) ||
-        reserve(t, t->st_persist, rows * sizeof(rg_persist_t)))
-        return -2;
-    HIP_TRY(t, hipMemcpyAsync(t->st_head.ptr, in->head, rows * sizeof(rg_ev_head_t), hipMemcpyHostToDevice, s));
-    HIP_TRY(t, hipMemcpyAsync(t->st_abcd32.ptr, in->abcd, rows * sizeof(rg_ev_quad32_t), hipMemcpyHostToDevice, s));
-    p.head = (const rg_ev_head_t *)t->st_head.ptr; p.abcd32 = (const rg::I32x4 *)t->st_abcd32.ptr;
-    if (sparse) {
-        if (reserve(t, t->st_gid, in->count * sizeof(uint32_t))) return -2;
-        HIP_TRY(t, hipMemcpyAsync(t->st_gid.ptr, in->gid, in->count * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        p.gid = (const uint32_t *)t->st_gid.ptr;
-    }
-    if (in->entry_count) {
-        if (reserve(t, t->st_terms32, in->entry_count * sizeof(int32_t))) return -2;
-        HIP_TRY(t, hipMemcpyAsync(t->st_terms32.ptr, in->entry_terms, in->entry_count * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        p.entry_terms32 = (const int32_t *)t->st_terms32.ptr;
-    }
-    p.reply = (rg_reply_t *)t->st_reply.ptr; p.logfx = (I64x2 *)t->st_logfx.ptr; p.persist = (rg_persist_t *)t->st_persist.ptr;
-    HIP_TRY(t, hipMemsetAsync(t->st_logfx.ptr, 0, rows * sizeof(I64x2), s));
-    HIP_TRY(t, hipMemsetAsync(t->st_persist.ptr, 0, rows * sizeof(rg_persist_t), s));
-    if (int rc = launch(t, p, sparse)) return rc;
-    HIP_TRY(t, hipMemcpyAsync(out->reply, t->st_reply.ptr, rows * sizeof(rg_reply_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(t, hipMemcpyAsync(out->logfx, t->st_logfx.ptr, rows * sizeof(I64x2), hipMemcpyDeviceToHost, s));
-    HIP_TRY(t, hipMemcpyAsync(out->persist, t->st_persist.ptr, rows * sizeof(rg_persist_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(t, hipStreamSynchronize(s));
-    return 0;
+    if (!out->reply || !out->logfx || !out->persist) return fail(t, -1, "rg_submit: head/ab/cd/reply/logfx/persist are required");
+    if (int rc = check_shape(t, shape_of(in), memspace == RG_MEM_HOST)) return rc;
+    return submit_compact(t, in, out, nullptr, memspace, "rg_submit32");
 }
 
 int rg_wide_body_workgroups(rg_table_t *t, uint64_t *count, int reset)
@@ -1544,63 +1551,8 @@ static int submit32c(rg_table_t *t, const rg_batch32_t *in, const rg_outcome32_t
     if (sparse && !in->gid) return fail(t, -1, "%s: gid is required (dense batches go through rg_submit32c)", who);
     const int wides = (out->wide.reply != nullptr) + (out->wide.logfx != nullptr) + (out->wide.persist != nullptr);
     if (wides != 0 && wides != 3) return fail(t, -1, "%s: the overflow columns come as all three or none", who);
-    rg_batch_t wide{};                              // the same shape rules as every other submission (rounds, count, gid list, entry bound)
-    wide.rounds = in->rounds; wide.count = in->count; wide.gid = in->gid; wide.head = in->head;
-    wide.ab = wide.cd = reinterpret_cast<const rg_ev_pair_t *>(in->abcd);      // presence only: check_batch does not read event fields
-    wide.entry_terms = reinterpret_cast<const int64_t *>(in->entry_terms); wide.entry_count = in->entry_count;
-    rg_reply_t dummy_r; rg_logfx_t dummy_l; rg_persist_t dummy_p;
-    const rg_outcome_t shape{&dummy_r, &dummy_l, &dummy_p};
-    if (int rc = check_batch(t, &wide, &shape, memspace == RG_MEM_HOST, list_rounds)) return rc;
-    if (in->count == 0) return 0;
-    if (bind(t)) return -2;
-    const size_t rows = (size_t)in->rounds * in->count;
-    rg::StepParams p = step_params(t, &wide);
-    if (memspace == RG_MEM_DEVICE) {
-        p.gid = in->gid; p.head = in->head; p.abcd32 = (const rg::I32x4 *)in->abcd;
-        p.entry_terms32 = in->entry_count ? in->entry_terms : nullptr;
-        p.out32 = (rg::I32x4 *)out->row; p.persist32 = (rg::I32x4 *)out->persist;
-        p.reply = out->wide.reply; p.logfx = (I64x2 *)out->wide.logfx; p.persist = out->wide.persist;
-        return launch(t, p, sparse);
-    }
-    if (memspace != RG_MEM_HOST) return fail(t, -1, "%s: unknown memspace %d", who, memspace);
-    hipStream_t s = t->stream;
-    if (reserve(t, t->st_head, rows * sizeof(rg_ev_head_t)) || reserve(t, t->st_abcd32, rows * sizeof(rg_ev_quad32_t)) ||
-        reserve(t, t->st_out32, rows * sizeof(rg_out32_t)) || reserve(t, t->st_persist32, rows * sizeof(rg_persist32_t)))
-        return -2;
-    if (wides && (reserve(t, t->st_reply, rows * sizeof(rg_reply_t)) || reserve(t, t->st_logfx, rows * sizeof(I64x2)) ||
-                  reserve(t, t->st_persist, rows * sizeof(rg_persist_t))))
-        return -2;
-    HIP_TRY(t, hipMemcpyAsync(t->st_head.ptr, in->head, rows * sizeof(rg_ev_head_t), hipMemcpyHostToDevice, s));
-    HIP_TRY(t, hipMemcpyAsync(t->st_abcd32.ptr, in->abcd, rows * sizeof(rg_ev_quad32_t), hipMemcpyHostToDevice, s));
-    p.head = (const rg_ev_head_t *)t->st_head.ptr; p.abcd32 = (const rg::I32x4 *)t->st_abcd32.ptr;
-    if (sparse) {
-        if (reserve(t, t->st_gid, in->count * sizeof(uint32_t))) return -2;
-        HIP_TRY(t, hipMemcpyAsync(t->st_gid.ptr, in->gid, in->count * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        p.gid = (const uint32_t *)t->st_gid.ptr;
-    }
-    if (in->entry_count) {
-        if (reserve(t, t->st_terms32, in->entry_count * sizeof(int32_t))) return -2;
-        HIP_TRY(t, hipMemcpyAsync(t->st_terms32.ptr, in->entry_terms, in->entry_count * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        p.entry_terms32 = (const int32_t *)t->st_terms32.ptr;
-    }
-    p.out32 = (rg::I32x4 *)t->st_out32.ptr; p.persist32 = (rg::I32x4 *)t->st_persist32.ptr;
-    HIP_TRY(t, hipMemsetAsync(t->st_persist32.ptr, 0, rows * sizeof(rg_persist32_t), s));       // conditional rows come back zeroed, as rg_submit's
-    if (wides) {
-        p.reply = (rg_reply_t *)t->st_reply.ptr; p.logfx = (I64x2 *)t->st_logfx.ptr; p.persist = (rg_persist_t *)t->st_persist.ptr;
-        HIP_TRY(t, hipMemsetAsync(t->st_reply.ptr, 0, rows * sizeof(rg_reply_t), s));
-        HIP_TRY(t, hipMemsetAsync(t->st_logfx.ptr, 0, rows * sizeof(I64x2), s));
-        HIP_TRY(t, hipMemsetAsync(t->st_persist.ptr, 0, rows * sizeof(rg_persist_t), s));
-    }
-    if (int rc = launch(t, p, sparse)) return rc;
-    HIP_TRY(t, hipMemcpyAsync(out->row, t->st_out32.ptr, rows * sizeof(rg_out32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(t, hipMemcpyAsync(out->persist, t->st_persist32.ptr, rows * sizeof(rg_persist32_t), hipMemcpyDeviceToHost, s));
-    if (wides) {
-        HIP_TRY(t, hipMemcpyAsync(out->wide.reply, t->st_reply.ptr, rows * sizeof(rg_reply_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(t, hipMemcpyAsync(out->wide.logfx, t->st_logfx.ptr, rows * sizeof(I64x2), hipMemcpyDeviceToHost, s));
-        HIP_TRY(t, hipMemcpyAsync(out->wide.persist, t->st_persist.ptr, rows * sizeof(rg_persist_t), hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(t, hipStreamSynchronize(s));
-    return 0;
+    if (int rc = check_shape(t, shape_of(in), memspace == RG_MEM_HOST, list_rounds)) return rc;
+    return submit_compact(t, in, wides ? &out->wide : nullptr, out, memspace, who);
 }
 
 int rg_submit32c(rg_table_t *t, const rg_batch32_t *in, const rg_outcome32_t *out, int memspace)
@@ -1717,33 +1669,18 @@ int rg_replicate(rg_table_t *t, uint32_t count, const uint32_t *gid, const uint8
         return 0;
     }
     if (memspace != RG_MEM_HOST) return fail(t, -1, "rg_replicate: unknown memspace %d", memspace);
+    uint32_t i = 0;
     if (gid)
-        for (uint32_t i = 0; i < count; i++) {
-            if (gid[i] >= t->G) return fail(t, -1, "rg_replicate: gid[%u]=%u out of range", i, gid[i]);
-            if (i && gid[i] <= gid[i - 1]) return fail(t, -1, "rg_replicate: gid must be strictly ascending (row %u)", i);
-        }
+        if (const int why = bad_gid_list(gid, count, t->G, &i))
+            return why == 1 ? fail(t, -1, "rg_replicate: gid[%u]=%u out of range", i, gid[i]) : fail(t, -1, "rg_replicate: gid must be strictly ascending (row %u)", i);
     hipStream_t s = t->stream;
     const size_t F = t->F;
-    if (reserve(t, t->st_sh, count * sizeof(rg_send_head_t)) || reserve(t, t->st_ss, count * F * sizeof(rg_send_t))) return -2;
-    if (gid) {
-        if (reserve(t, t->st_gid, count * sizeof(uint32_t))) return -2;
-        HIP_TRY(t, hipMemcpyAsync(t->st_gid.ptr, gid, count * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        p.gid = (const uint32_t *)t->st_gid.ptr;
-    }
-    if (heartbeat) {
-        if (reserve(t, t->st_hb, count)) return -2;
-        HIP_TRY(t, hipMemcpyAsync(t->st_hb.ptr, heartbeat, count, hipMemcpyHostToDevice, s));
-        p.heartbeat = (const uint8_t *)t->st_hb.ptr;
-    }
-    if (in_flight) {
-        if (reserve(t, t->st_fl, count * F * sizeof(uint16_t))) return -2;
-        HIP_TRY(t, hipMemcpyAsync(t->st_fl.ptr, in_flight, count * F * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-        p.in_flight = (const uint16_t *)t->st_fl.ptr;
-    }
-    p.head = (rg_send_head_t *)t->st_sh.ptr; p.send = (rg_send_t *)t->st_ss.ptr;
+    if (stage_out(t, t->aux[X_SH], count, &p.head) || stage_out(t, t->aux[X_SS], count * F, &p.send)) return -2;
+    if (gid && stage_in(t, t->st[C_GID], gid, count, s, &p.gid)) return -2;
+    if (heartbeat && stage_in(t, t->aux[X_HB], heartbeat, count, s, &p.heartbeat)) return -2;
+    if (in_flight && stage_in(t, t->aux[X_FL], in_flight, count * F, s, &p.in_flight)) return -2;
     HIP_TRY(t, rg::launch_replicate(p, (int)t->F, s));
-    HIP_TRY(t, hipMemcpyAsync(head, t->st_sh.ptr, count * sizeof(rg_send_head_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(t, hipMemcpyAsync(send, t->st_ss.ptr, count * F * sizeof(rg_send_t), hipMemcpyDeviceToHost, s));
+    if (stage_back(t, t->aux[X_SH], head, count, s) || stage_back(t, t->aux[X_SS], send, count * F, s)) return -2;
     HIP_TRY(t, hipStreamSynchronize(s));
     return 0;
 }
@@ -1776,29 +1713,20 @@ int rg_timers_update(rg_table_t *t, uint32_t rounds, uint32_t count, const uint3
     if (bind(t)) return -2;
     hipStream_t s = t->stream;
     const size_t rows = (size_t)rounds * count;
-    const rg_reply_t *d_reply = reply;
-    const uint32_t *d_gid = gid;
+    rg::TimerParams base = timer_params(t);
+    base.count = count; base.gid = gid; base.reply = reply;
     if (memspace == RG_MEM_HOST) {
-        if (reserve(t, t->st_reply, rows * sizeof(rg_reply_t))) return -2;
-        HIP_TRY(t, hipMemcpyAsync(t->st_reply.ptr, reply, rows * sizeof(rg_reply_t), hipMemcpyHostToDevice, s));
-        d_reply = (const rg_reply_t *)t->st_reply.ptr;
-        if (gid) {
-            for (uint32_t i = 0; i < count; i++)
-                if (gid[i] >= t->G || (i && gid[i] <= gid[i - 1])) return fail(t, -1, "rg_timers_update: bad gid list at row %u", i);
-            if (reserve(t, t->st_gid, count * sizeof(uint32_t))) return -2;
-            HIP_TRY(t, hipMemcpyAsync(t->st_gid.ptr, gid, count * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-            d_gid = (const uint32_t *)t->st_gid.ptr;
-        }
+        if (stage_in(t, t->st[C_REPLY], reply, rows, s, &base.reply)) return -2;
+        uint32_t i = 0;
+        if (gid && bad_gid_list(gid, count, t->G, &i)) return fail(t, -1, "rg_timers_update: bad gid list at row %u", i);
+        if (gid && stage_in(t, t->st[C_GID], gid, count, s, &base.gid)) return -2;
     } else if (memspace != RG_MEM_DEVICE) {
         return fail(t, -1, "rg_timers_update: unknown memspace %d", memspace);
     }
-    for (uint32_t r0 = 0; r0 < rounds; r0 += 64) {               // <= 64 timestamps travel in the kernel arguments
-        rg::TimerParams p = timer_params(t);
-        p.rounds = rounds - r0 < 64 ? rounds - r0 : 64; p.count = count; p.gid = d_gid;
-        p.reply = d_reply + (size_t)r0 * count;
-        for (uint32_t k = 0; k < p.rounds; k++) p.now[k] = now[r0 + k];
-        HIP_TRY(t, rg::launch_timers_update(p, s));
-    }
+    if (int rc = clock_chunks(t, rounds, now, base, [&](rg::TimerParams &p, uint32_t r0) {
+            p.reply = base.reply + (size_t)r0 * count;
+            return rg::launch_timers_update(p, s);
+        })) return rc;
     if (memspace == RG_MEM_HOST) HIP_TRY(t, hipStreamSynchronize(s));
     return 0;
 }
@@ -1811,22 +1739,17 @@ int rg_timers_update32(rg_table_t *t, uint32_t rounds, const rg_out32_t *row, co
     hipStream_t s = t->stream;
     const uint32_t count = t->G;
     const size_t rows = (size_t)rounds * count;
-    const rg::I32x4 *d_row = (const rg::I32x4 *)row, *d_per = (const rg::I32x4 *)persist32;
+    rg::TimerParams base = timer_params(t);
+    base.count = count; base.out32 = (const rg::I32x4 *)row; base.persist32 = (const rg::I32x4 *)persist32;
     if (memspace == RG_MEM_HOST) {
-        if (reserve(t, t->st_out32, rows * sizeof(rg_out32_t)) || reserve(t, t->st_persist32, rows * sizeof(rg_persist32_t))) return -2;
-        HIP_TRY(t, hipMemcpyAsync(t->st_out32.ptr, row, rows * sizeof(rg_out32_t), hipMemcpyHostToDevice, s));
-        HIP_TRY(t, hipMemcpyAsync(t->st_persist32.ptr, persist32, rows * sizeof(rg_persist32_t), hipMemcpyHostToDevice, s));
-        d_row = (const rg::I32x4 *)t->st_out32.ptr; d_per = (const rg::I32x4 *)t->st_persist32.ptr;
+        if (stage_in(t, t->st[C_OUT32], row, rows, s, &base.out32) || stage_in(t, t->st[C_PERSIST32], persist32, rows, s, &base.persist32)) return -2;
     } else if (memspace != RG_MEM_DEVICE) {
         return fail(t, -1, "rg_timers_update32: unknown memspace %d", memspace);
     }
-    for (uint32_t r0 = 0; r0 < rounds; r0 += 64) {               // <= 64 timestamps travel in the kernel arguments
-        rg::TimerParams p = timer_params(t);
-        p.rounds = rounds - r0 < 64 ? rounds - r0 : 64; p.count = count;
-        p.out32 = d_row + (size_t)r0 * count; p.persist32 = d_per + (size_t)r0 * count;
-        for (uint32_t k = 0; k < p.rounds; k++) p.now[k] = now[r0 + k];
-        HIP_TRY(t, rg::launch_timers_update(p, s));
-    }
+    if (int rc = clock_chunks(t, rounds, now, base, [&](rg::TimerParams &p, uint32_t r0) {
+            p.out32 = base.out32 + (size_t)r0 * count; p.persist32 = base.persist32 + (size_t)r0 * count;
+            return rg::launch_timers_update(p, s);
+        })) return rc;
     if (memspace == RG_MEM_HOST) HIP_TRY(t, hipStreamSynchronize(s));
     return 0;
 }
@@ -1851,8 +1774,7 @@ int rg_timers_expired_epochs(rg_table_t *t, int64_t now, uint32_t *out_gid, uint
     uint32_t *d_out = out_gid, *d_ep = out_epoch;
     const size_t cap = capacity ? capacity : 1;
     if (memspace == RG_MEM_HOST) {
-        if (reserve(t, t->st_tgid, 2 * cap * sizeof(uint32_t))) return -2;      // gids, then epochs
-        d_out = (uint32_t *)t->st_tgid.ptr;
+        if (stage_out(t, t->aux[X_TGID], 2 * cap, &d_out)) return -2;          // gids, then epochs
         d_ep = out_epoch ? d_out + cap : nullptr;
     } else if (memspace != RG_MEM_DEVICE) {
         return fail(t, -1, "rg_timers_expired: unknown memspace %d", memspace);
@@ -1908,29 +1830,20 @@ int rg_health_update(rg_table_t *t, uint32_t rounds, uint32_t count, const uint3
     if (bind(t)) return -2;
     hipStream_t s = t->stream;
     const size_t rows = (size_t)rounds * count;
-    const rg_ev_head_t *d_head = head; const rg_reply_t *d_reply = reply; const uint32_t *d_gid = gid;
+    rg::HealthParams base = health_params(t);
+    base.count = count; base.gid = gid; base.head = head; base.reply = reply;
     if (memspace == RG_MEM_HOST) {
-        if (reserve(t, t->st_head, rows * sizeof(rg_ev_head_t)) || reserve(t, t->st_reply, rows * sizeof(rg_reply_t))) return -2;
-        HIP_TRY(t, hipMemcpyAsync(t->st_head.ptr, head, rows * sizeof(rg_ev_head_t), hipMemcpyHostToDevice, s));
-        HIP_TRY(t, hipMemcpyAsync(t->st_reply.ptr, reply, rows * sizeof(rg_reply_t), hipMemcpyHostToDevice, s));
-        d_head = (const rg_ev_head_t *)t->st_head.ptr; d_reply = (const rg_reply_t *)t->st_reply.ptr;
-        if (gid) {
-            for (uint32_t i = 0; i < count; i++)
-                if (gid[i] >= t->G || (i && gid[i] <= gid[i - 1])) return fail(t, -1, "rg_health_update: bad gid list at row %u", i);
-            if (reserve(t, t->st_gid, count * sizeof(uint32_t))) return -2;
-            HIP_TRY(t, hipMemcpyAsync(t->st_gid.ptr, gid, count * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-            d_gid = (const uint32_t *)t->st_gid.ptr;
-        }
+        if (stage_in(t, t->st[C_HEAD], head, rows, s, &base.head) || stage_in(t, t->st[C_REPLY], reply, rows, s, &base.reply)) return -2;
+        uint32_t i = 0;
+        if (gid && bad_gid_list(gid, count, t->G, &i)) return fail(t, -1, "rg_health_update: bad gid list at row %u", i);
+        if (gid && stage_in(t, t->st[C_GID], gid, count, s, &base.gid)) return -2;
     } else if (memspace != RG_MEM_DEVICE) {
         return fail(t, -1, "rg_health_update: unknown memspace %d", memspace);
     }
-    for (uint32_t r0 = 0; r0 < rounds; r0 += 64) {
-        rg::HealthParams p = health_params(t);
-        p.rounds = rounds - r0 < 64 ? rounds - r0 : 64; p.count = count; p.gid = d_gid;
-        p.head = d_head + (size_t)r0 * count; p.reply = d_reply + (size_t)r0 * count;
-        for (uint32_t k = 0; k < p.rounds; k++) p.now[k] = now[r0 + k];
-        HIP_TRY(t, rg::launch_health_update(p, s));
-    }
+    if (int rc = clock_chunks(t, rounds, now, base, [&](rg::HealthParams &p, uint32_t r0) {
+            p.head = base.head + (size_t)r0 * count; p.reply = base.reply + (size_t)r0 * count;
+            return rg::launch_health_update(p, s);
+        })) return rc;
     if (memspace == RG_MEM_HOST) HIP_TRY(t, hipStreamSynchronize(s));
     return 0;
 }
@@ -1943,23 +1856,17 @@ int rg_health_update32(rg_table_t *t, uint32_t rounds, const rg_ev_head_t *head,
     hipStream_t s = t->stream;
     const uint32_t count = t->G;
     const size_t rows = (size_t)rounds * count;
-    const rg_ev_head_t *d_head = head;
-    const rg::I32x4 *d_row = (const rg::I32x4 *)row;
+    rg::HealthParams base = health_params(t);
+    base.count = count; base.head = head; base.out32 = (const rg::I32x4 *)row;
     if (memspace == RG_MEM_HOST) {
-        if (reserve(t, t->st_head, rows * sizeof(rg_ev_head_t)) || reserve(t, t->st_out32, rows * sizeof(rg_out32_t))) return -2;
-        HIP_TRY(t, hipMemcpyAsync(t->st_head.ptr, head, rows * sizeof(rg_ev_head_t), hipMemcpyHostToDevice, s));
-        HIP_TRY(t, hipMemcpyAsync(t->st_out32.ptr, row, rows * sizeof(rg_out32_t), hipMemcpyHostToDevice, s));
-        d_head = (const rg_ev_head_t *)t->st_head.ptr; d_row = (const rg::I32x4 *)t->st_out32.ptr;
+        if (stage_in(t, t->st[C_HEAD], head, rows, s, &base.head) || stage_in(t, t->st[C_OUT32], row, rows, s, &base.out32)) return -2;
     } else if (memspace != RG_MEM_DEVICE) {
         return fail(t, -1, "rg_health_update32: unknown memspace %d", memspace);
     }
-    for (uint32_t r0 = 0; r0 < rounds; r0 += 64) {
-        rg::HealthParams p = health_params(t);
-        p.rounds = rounds - r0 < 64 ? rounds - r0 : 64; p.count = count;
-        p.head = d_head + (size_t)r0 * count; p.out32 = d_row + (size_t)r0 * count;
-        for (uint32_t k = 0; k < p.rounds; k++) p.now[k] = now[r0 + k];
-        HIP_TRY(t, rg::launch_health_update(p, s));
-    }
+    if (int rc = clock_chunks(t, rounds, now, base, [&](rg::HealthParams &p, uint32_t r0) {
+            p.head = base.head + (size_t)r0 * count; p.out32 = base.out32 + (size_t)r0 * count;
+            return rg::launch_health_update(p, s);
+        })) return rc;
     if (memspace == RG_MEM_HOST) HIP_TRY(t, hipStreamSynchronize(s));
     return 0;
 }
@@ -1971,10 +1878,10 @@ int rg_health_failure(rg_table_t *t, uint32_t n, const uint32_t *gid, const uint
     if (n == 0) return 0;
     if (bind(t)) return -2;
     hipStream_t s = t->stream;
-    if (reserve(t, t->st_hgid, n * sizeof(uint32_t)) || reserve(t, t->st_hslot, n) || reserve(t, t->st_hflag, n)) return -2;
-    HIP_TRY(t, hipMemcpyAsync(t->st_hgid.ptr, gid, n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    HIP_TRY(t, hipMemcpyAsync(t->st_hslot.ptr, slot, n, hipMemcpyHostToDevice, s));
-    HIP_TRY(t, hipMemcpyAsync(t->st_hflag.ptr, flags, n, hipMemcpyHostToDevice, s));
+    const uint32_t *d_gid = nullptr;
+    const uint8_t *d_slot = nullptr, *d_flags = nullptr;
+    const uint16_t *d_done = nullptr;
+    if (stage_in(t, t->aux[X_HGID], gid, n, s, &d_gid) || stage_in(t, t->aux[X_HSLOT], slot, n, s, &d_slot) || stage_in(t, t->aux[X_HFLAG], flags, n, s, &d_flags)) return -2;
     rg::HealthParams p = health_params(t);
     p.now[0] = now;
     std::vector<uint16_t> done;
@@ -1988,11 +1895,9 @@ int rg_health_failure(rg_table_t *t, uint32_t n, const uint32_t *gid, const uint
             const uint32_t at = first_of.emplace(((uint64_t)gid[i] << 8) | slot[i], i).first->second;
             if (done[at] != 0xFFFFu) done[at] += 1;
         }
-        if (reserve(t, t->st_hdone, n * sizeof(uint16_t))) return -2;
-        HIP_TRY(t, hipMemcpyAsync(t->st_hdone.ptr, done.data(), n * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+        if (stage_in(t, t->aux[X_HDONE], done.data(), n, s, &d_done)) return -2;
     }
-    HIP_TRY(t, rg::launch_health_failure(p, n, (const uint32_t *)t->st_hgid.ptr, (const uint8_t *)t->st_hslot.ptr,
-                                         (const uint8_t *)t->st_hflag.ptr, t->in_flight ? (const uint16_t *)t->st_hdone.ptr : nullptr, s));
+    HIP_TRY(t, rg::launch_health_failure(p, n, d_gid, d_slot, d_flags, d_done, s));
     HIP_TRY(t, hipStreamSynchronize(s));
     return 0;
 }
@@ -2004,14 +1909,13 @@ int rg_ready(rg_table_t *t, int64_t now, int32_t critical_point, int64_t cool_do
     hipStream_t s = t->stream;
     uint8_t *d_ready = ready;
     if (memspace == RG_MEM_HOST) {
-        if (reserve(t, t->st_ready, t->G)) return -2;
-        d_ready = (uint8_t *)t->st_ready.ptr;
+        if (stage_out(t, t->aux[X_READY], t->G, &d_ready)) return -2;
     } else if (memspace != RG_MEM_DEVICE) {
         return fail(t, -1, "rg_ready: unknown memspace %d", memspace);
     }
     HIP_TRY(t, rg::launch_ready(health_params(t), now, critical_point, cool_down_ms, d_ready, s));
     if (memspace == RG_MEM_HOST) {
-        HIP_TRY(t, hipMemcpyAsync(ready, d_ready, t->G, hipMemcpyDeviceToHost, s));
+        if (int rc = stage_back(t, t->aux[X_READY], ready, t->G, s)) return rc;
         HIP_TRY(t, hipStreamSynchronize(s));
     }
     return 0;
