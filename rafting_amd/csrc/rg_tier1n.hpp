@@ -31,6 +31,7 @@ typedef int32_t sw;                 // sign word: bit 31 is the truth value, bit
 __device__ __forceinline__ sw s_lt(int32_t x, int32_t y) { return (int32_t)((uint32_t)x - (uint32_t)y); }                  // x < y   (|x - y| < 2^31)
 __device__ __forceinline__ sw s_ne(int32_t x, int32_t y) { return (int32_t)(((uint32_t)x ^ (uint32_t)y) + 0x7FFFFFFFu); }   // x != y  (x ^ y < 2^31: operands that differ in bit 31 read as EQUAL)
 __device__ __forceinline__ sw s_pos(int32_t x) { return (int32_t)(0u - (uint32_t)x); }                                      // x > 0   (x > -2^31)
+__device__ __forceinline__ sw s_nz(int32_t x) { return (int32_t)((uint32_t)x | (0u - (uint32_t)x)); }                             // x != 0  (any x; for a launch parameter: scalar, made once per launch)
 __device__ __forceinline__ uint32_t push_bit(uint32_t acc, sw w) { return (acc << 1) | ((uint32_t)w >> 31); }              // v_alignbit_b32
 
 // ---- the class word of a row (made by the I/O wavefront: class_word() in rg_step.hpp) --------------------------------------
@@ -280,14 +281,20 @@ __device__ __forceinline__ sw tier1n(const StepParams &p, GroupN &g, PeersNarrow
             // One sub-block per row class, each behind its own ballot, and the conversion tail behind one more: three election rows of four are
             // vote replies that are merely counted (config 3: 1.19 % of the rows, 54 % of the wave-rounds; timeouts 12 %, vote requests 9 %), and a
             // launch ends with its slowest workgroup — the one that meets such a row in 61 of its 64 rounds.
+            // Each class ORs the predicate bits that only it can set into pw_el at their places (bit k of pw_el is bit 7 + k of the predicate word: 6 vq,
+            // 5 vq_success, 4 reset, 3 conv, 2 to_lead, 1 to_pre, 0 to_candidate); `conv`, which every class can set, goes in once at the end. A class that
+            // is skipped leaves no zeroed word behind to be copied at the joins and pushed: a round with a counted vote reply 281 -> 271 instructions.
+            // The block reads g.prepared and g.rc, not the round's snapshots of them: a lane is in one class, so for an election lane they are the same
+            // values, and the snapshots need not be kept in registers of their own across the rare block (six copies per election round; with the scalar
+            // sign words of the two launch parameters below, 271 -> 264).
             const int32_t term1 = term + 1;
             const sw is_pv = cw_bit(cw, CW_PV);
             const sw not_f = s_pos(role), not_c = s_ne(role, RG_CANDIDATE), not_l = s_ne(role, RG_LEADER);
             sw conv = ack_down, conv_self = 0, to_c = 0, win_rv = 0, late_higher = 0, count = 0, el_fast = ack_down;
-            sw to_pre = 0, to_lead = 0, vq = 0, vq_success = 0, reset = 0, rv_new = 0, no_vote = 0;
+            sw to_pre = 0, to_lead = 0, resp_own = 0, no_vote = 0;
             // vote replies (member/Candidate.java:121-134, member/Follower.java:258-270)
             const sw vr_shape = cw_bit(cw, CW_VR) & ~nallow;
-            const sw to_kind = cw_bit(cw, CW_TO) & ~nallow & (s_pos(aux) | ((p.require_fence != 0) ? 0 : -1));      // (an un-fenced row where fences are required: general handlers, RG_BAD_EVENT)
+            const sw to_kind = cw_bit(cw, CW_TO) & ~nallow & (s_pos(aux) | ~s_nz(p.require_fence));      // (an un-fenced row where fences are required: general handlers, RG_BAD_EVENT)
             const sw vq_shape = cw_bit(cw, CW_VQ) & ~nallow;
             const uint64_t b_vr = __builtin_amdgcn_ballot_w64(vr_shape < 0), b_to = __builtin_amdgcn_ballot_w64(to_kind < 0), b_vq = __builtin_amdgcn_ballot_w64(vq_shape < 0);
             if (b_vr != 0) {
@@ -310,46 +317,58 @@ __device__ __forceinline__ sw tier1n(const StepParams &p, GroupN &g, PeersNarrow
                 conv = conv | (vr_cur & x_Ta) | vr_win | (late_higher & ~s_lt(a, term));
                 el_fast = el_fast | vr_cur | late_higher | late_noop | vote_drop;
                 any_drop = any_drop | vote_drop;
+                pw_el = (uint32_t)to_c >> 31;                           // bit 0 (the first class: pw_el is 0 so far)
             }
             // timeouts (aux 0 = whoever is current; context/RaftRoutine.java:70)
             if (b_to != 0) {
                 const sw to_stale = to_kind & s_pos(aux) & x_aux;
                 const sw to_live = to_kind & ~to_stale;
-                const sw pre = (p.pre_vote != 0) ? -1 : 0;
+                const sw pre = s_nz(p.pre_vote);
                 const sw to_cand = to_live & ((~not_f & ~pre) | ~not_c);
                 to_pre = to_live & ~not_f & pre;
                 to_lead = to_live & ~not_l;
                 conv_self = conv_self | to_cand;
                 to_c = to_c | to_cand;
                 conv = conv | to_cand | to_pre;
-                reset = to_lead;
                 el_fast = el_fast | to_kind;                            // (stale | pre | cand | lead: a timeout always lands in one of them)
                 any_drop = any_drop | to_stale;
+                const uint32_t lead_bit = (uint32_t)to_lead >> 31;      // reset (a Leader's timeout re-arms its timer) and to_lead are the same truth value
+                pw_el = pw_el | (lead_bit << 4) | push_bit(push_bit(lead_bit, to_pre), to_cand);      // bits 4 and 2, 1, 0
             }
             // RequestVote / PreVote at a Follower that has a log (member/Follower.java:91-127, 193-207)
             if (b_vq != 0) {
                 const sw is_pvq = cw_bit(cw, CW_PVQ);
-                vq = vq_shape & ~not_f & ~s_lt(rc, 1);
+                const sw vq = vq_shape & ~not_f & ~s_lt(g.rc, 1);
                 const sw utd = s_lt(lt, c) | (~s_ne(c, lt) & ~s_lt(b, last));      // Follower.logUpToDate with a last entry
                 const sw pv_judge = vq & is_pvq & x_ta & td;            // else failure(currentTerm), no timer touched
                 const sw rv_same = vq & ~is_pvq & ~x_ta & ~s_lt(a, term);
                 const sw voted_other = s_ne(voted, slot) | voted;       // (votedFor == NO_NODE is nobody's slot)
-                rv_new = vq & ~is_pvq & x_ta;
+                const sw rv_new = vq & ~is_pvq & x_ta;
+                const sw vq_success = ((pv_judge | rv_new) & utd) | (rv_same & ~voted_other);
                 no_vote = rv_new & ~utd;
-                vq_success = ((pv_judge | rv_new) & utd) | (rv_same & ~voted_other);
-                reset = reset | pv_judge;
+                resp_own = vq & ~rv_new;                                // the answer carries this node's term, not the request's
                 conv = conv | rv_new;
                 el_fast = el_fast | vq;
+                pw_el = pw_el | (push_bit(push_bit(push_bit(0u, vq), vq_success), pv_judge) << 4);      // bits 6, 5, 4
             }
-            // RaftRoutine.convertTo + RaftMember.<init> for the lanes in `conv`; what else a row changes beyond the vote count
-            const sw lead_prepare = to_lead & ~prep;                    // a new Leader's first tick: Leader.prepareReplication (member/Leader.java:30-50)
-            if (__builtin_amdgcn_ballot_w64((conv | lead_prepare | late_higher) < 0) != 0) {
+            // RaftRoutine.convertTo + RaftMember.<init> for the lanes in `conv`; what else a row changes beyond the vote count.
+            // What does not need the tail is stated ahead of its branch. (Holding the ballot in scalars of its own with that work pinned between it and the
+            // branch — s_cmp + s_cbranch_scc instead of s_cbranch_vccz — measured the same, and gathering the ballot per class cost four instructions:
+            // profiles/election_round_ab.jsonl.)
+            const sw lead_prepare = to_lead & ~g.prepared;              // a new Leader's first tick: Leader.prepareReplication (member/Leader.java:30-50)
+            const uint64_t b_conv = __builtin_amdgcn_ballot_w64((conv | lead_prepare | late_higher) < 0);
+            const int32_t votes_counted = g.votes + (int32_t)((uint32_t)count >> 31);    // (a counted vote never converts: the tail's lanes and these are disjoint)
+            out.resp = (resp_own < 0) ? term : a;                       // (only read for the vote requests)
+            pw_el = pw_el | (((uint32_t)conv >> 28) & 8u);              // bit 3
+            done = done | el_fast;
+            g.votes = votes_counted;
+            if (b_conv != 0) {
                 const bool m_conv = conv < 0, m_winrv = win_rv < 0;
                 const int32_t new_role = (win_rv < 0) ? RG_LEADER : ((to_c < 0) ? RG_CANDIDATE : RG_FOLLOWER);
                 const int32_t new_term = (to_c < 0) ? term1 : (((win_rv | to_pre) < 0) ? term : a);
                 const int32_t new_vote = (conv_self < 0) ? p.self : ((to_pre < 0) ? voted : ((no_vote < 0) ? RG_NO_NODE : slot));
                 if (lead_prepare < 0) {
-                    pe.store_prepare(epoch, ((rc > 0) ? last : epoch) + 1);
+                    pe.store_prepare(epoch, ((g.rc > 0) ? last : epoch) + 1);
                     g.pending = 0;
                 }
                 g.elected_epoch = m_winrv ? (uint32_t)repoch : ((late_higher < 0) ? 0u : g.elected_epoch);      // Candidate.java:75-79 / head.abortRequests()
@@ -359,22 +378,16 @@ __device__ __forceinline__ sw tier1n(const StepParams &p, GroupN &g, PeersNarrow
                 g.voted_for = m_conv ? new_vote : g.voted_for;
                 g.role_epoch = g.role_epoch + (m_conv ? 1u : 0u);
                 g.td = (g.td & ~conv) | to_pre;
-                g.votes = m_conv ? 1 : g.votes;
+                g.votes = m_conv ? 1 : votes_counted;
                 g.leader = m_conv ? RG_NO_NODE : g.leader;
                 g.prepared = (g.prepared & ~conv) | lead_prepare;
                 g.peers_dirty = g.peers_dirty | lead_prepare;
             }
-            g.votes = g.votes + (int32_t)((uint32_t)count >> 31);       // (a counted vote never converts)
-            out.resp = ((vq & ~rv_new) < 0) ? term : a;                 // (only read for the vote requests)
-            pw_el = push_bit(0u, vq);
-            pw_el = push_bit(pw_el, vq_success);
-            pw_el = push_bit(pw_el, reset);
-            pw_el = push_bit(pw_el, conv);
-            pw_el = push_bit(pw_el, to_lead);
-            pw_el = push_bit(pw_el, to_pre);
-            pw_el = push_bit(pw_el, to_c);
-            done = done | el_fast;
         }
+        // (recache() reads role, rc, prepared, nallow, epoch_index and last, and of these only rc and prepared — the rare block — and role and prepared — the
+        // tail — change here in a way the words can see: `last` enters as "epoch_index < last" at a Follower, where only an AppendEntries that the word has let
+        // through moves it, upwards. Re-caching in those two places instead of here takes 6 instructions off a counted vote reply and puts 2 copies on the
+        // main path, which every round of every workgroup pays; same-box it was no faster: profiles/election_round_ab.jsonl.)
         g.recache();
     }
     pw = push_bit(pw, any_drop);
