@@ -863,6 +863,64 @@ typedef struct {
 } rg_routed_t;
 int rg_route32(rg_assembler_t *a, const rg_decided_t *in, const rg_routed_t *out, int memspace);
 
+/* ---- CARRYING DEFERRED EVENTS INTO THE NEXT RUN (new symbols only; the ABI stays 6) ---------------------------------------------------------------
+ * An event is DEFERRED when its group already has max_rounds events in the batch or falls outside the `capacity` smallest groups of the run. Above, the host
+ * puts such events at the head of its next arrival log by hand — which means waiting for the run, reading stats and deferred[], copying rows and shifting every
+ * reader's index. A CARRY moves that recipe onto the device: the assembler keeps what it deferred, the next run takes it first, in order, and the route tells
+ * every reader where its event went. It is OFF by default; with the carry off every entry point behaves exactly as described above, bit for bit.
+ *
+ * rg_assembler_carry_enable gives the assembler two carries of carry_capacity slots each, in its own device memory (0 takes them away again); it waits for the
+ * table's stream, sizes the scratch for max_events + max_expired + carry_capacity positions and leaves both carries empty (if it runs out of memory, -2, the
+ * assembler holds no scratch and rg_assemble32 refuses it until an enable succeeds). A slot holds a complete compact row
+ * (gid, head, abcd). The two carries alternate: a run reads one and leaves the other; which is which follows the host's count of the calls and is never device data.
+ *
+ * THE SEQUENCE S of a run on a carrying assembler: the expired source as above; then the carry, slots c = 0 .. q - 1 — q is the count the previous run left, 0
+ * after enable and after reset, read on the device —; then the arrival log as above. A slot moves into its cell verbatim; its id, in origin and in deferred[], is
+ * RG_ASM_CARRIED | c. For the same inputs the columns gid, count, rounds, head and abcd equal, bit for bit, what a run without a carry produces when the host
+ * prepends the deferred rows to its log by hand; origin and deferred differ by that relabelling of the ids only.
+ *
+ * AFTER THE RUN the events it deferred, in S order, are the next carry: slot p holds the event at position p of the run's deferred sequence — what deferred[p]
+ * names, whatever deferred_capacity is (deferred may be NULL with a capacity of 0) —, a fired ticket as the row the assembler would have made of it,
+ * {RG_HDR_MAKE of RG_EV_TIMEOUT, epoch} with a zero quad. The carry takes the first min(stats[1], carry_capacity) of them; stats[3], 0 on an assembler without a
+ * carry, is the number that did not fit, the SPILLED events. Spilled arrivals and tickets are still with the host, their ids are deferred[p] for p >=
+ * carry_capacity; a spilled event that was itself carried can be fetched with rg_assembler_carry_read of RG_CARRY_LAST until the next run. An event with a bad
+ * gid is never carried. Every output and the new carry are a function of the inputs and the old carry alone, bit for bit, run after run.
+ *
+ * rg_assembler_carry_reset empties the carry the next run will read (asynchronous on the table's stream). rg_assembler_carry_read copies a carry to host arrays:
+ * *count = its slots, of which the first min(*count, capacity) are written; it waits for the stream: for draining, recovery and tests.
+ *
+ * rg_route32_carry does everything rg_route32 does, for the last run of a carrying assembler, and on top of it:
+ *   - carried->cell / row / persist32 hold [carry_capacity] entries. For every slot c < q that the routed run read, cell[c] is ALWAYS written; row[c] and
+ *     persist32[c] are written iff the slot was placed, and iff its flags carry RG_F_PERSIST, as for an arrival. Entries >= q are NOT TOUCHED.
+ *   - every event the run read has ONE of four values in its cell entry — cell[k], expired_cell[j], carried->cell[c] —: the cell index (below 2^31);
+ *     RG_ROUTE_CARRIED | s, the event was deferred into slot s of the carry the NEXT run reads; RG_ROUTE_SPILLED, it was deferred and the carry had no room: the
+ *     host still owns it; RG_ROUTE_NONE, its gid was bad.
+ *   - a reader follows k -> RG_ROUTE_CARRIED | s -> carried->cell[s] of the NEXT run's route, and so on, until it reads a cell.
+ * Plain rg_route32 on a carrying assembler stays what it is: a deferred event gets RG_ROUTE_NONE, a cell that answers a carried slot is routed nowhere.
+ *
+ * HOST DUTIES. rg_index_base_set on a group that has carried rows is the host's error: the rows stay relative to the old base. An entry-terms slot that a
+ * carried AppendEntries row addresses through `aux` must stay in place in the array handed to later launches until that row's cell is routed; a row with
+ * RG_HDR_SAME_TERM needs nothing.
+ *
+ * MEMSPACES as for the two calls above. The carry always lives in the assembler's device memory: an RG_MEM_HOST run reads it and leaves it there. In
+ * RG_MEM_DEVICE everything is asynchronous on the table's stream, grids are sized from the capacities — carry_capacity among them — and leave early on the counts
+ * they read; no kernel waits for another workgroup.
+ * Refused (-1, with a message, before any launch): enabling a carry with max_events, max_expired or carry_capacity at or above 2^30 (bit 30 marks a carried id);
+ * rg_assembler_carry_reset, rg_assembler_carry_read and rg_route32_carry on an assembler without a carry; a carried->capacity that differs from the carry's; a
+ * missing carried column; C x D above 2^31 (the RG_ROUTE_CARRIED bit must stay free); an unknown `which`; and rg_assemble32 on a carrying assembler whose table
+ * has RG_OPT_AUTO_INDEX_BASE set: a base that a decided RG_EV_LOG_FLUSH row moves would leave the same group's carried rows relative to the old base. */
+#define RG_ASM_CARRIED   0x40000000u   /* origin / deferred id of carry slot c: RG_ASM_CARRIED | c */
+#define RG_ROUTE_CARRIED 0x80000000u   /* a routed `cell` entry: the event was deferred into slot (value & 0x3FFFFFFF) of the carry the NEXT run reads */
+#define RG_ROUTE_SPILLED 0xFFFFFFFEu   /* deferred, and the carry had no room: the host still owns this event */
+#define RG_CARRY_NEXT 0                /* the carry the next run will read */
+#define RG_CARRY_LAST 1                /* the carry the last run read (intact until the next run) */
+int rg_assembler_carry_enable(rg_assembler_t *a, uint32_t carry_capacity);   /* 0 disables; (re)sizes scratch, empties the carry */
+int rg_assembler_carry_reset(rg_assembler_t *a);                             /* empties RG_CARRY_NEXT; asynchronous on the table's stream */
+int rg_assembler_carry_read(rg_assembler_t *a, int which, uint32_t capacity, uint32_t *count,
+                            uint32_t *gid, rg_ev_head_t *head, rg_ev_quad32_t *abcd);   /* host arrays, synchronous: draining, recovery, tests */
+typedef struct { uint32_t capacity; uint32_t *cell; rg_out32_t *row; rg_persist32_t *persist32; } rg_routed_carry_t;   /* [capacity] each */
+int rg_route32_carry(rg_assembler_t *a, const rg_decided_t *in, const rg_routed_t *out, const rg_routed_carry_t *carried, int memspace);
+
 /* ---- device memory helpers (so a host without its own HIP binding can keep batches in HBM) --- */
 /* Page-locked host memory for RG_MEM_HOST batches (JNI: wrap it with NewDirectByteBuffer): staging then runs at PCIe
  * speed instead of through the driver's pageable bounce buffers. */

@@ -156,10 +156,17 @@ class CRouted(C.Structure):            # rg_routed_t
                 ("send_list", C.c_void_p), ("send_capacity", C.c_uint32), ("send_offset", C.c_void_p), ("counts", C.c_void_p)]
 
 
+class CRoutedCarry(C.Structure):       # rg_routed_carry_t
+    _fields_ = [("capacity", C.c_uint32), ("cell", C.c_void_p), ("row", C.c_void_p), ("persist32", C.c_void_p)]
+
+
 ROUTE_NONE = 0xFFFFFFFF                                   # rg_routed_t.cell: a deferred event, or one with a bad gid
 ROUTE_ITEM_DT = np.dtype([("cell", np.uint32), ("gid", np.uint32)])       # rg_route_item_t: persist_list, attention
 SEND_ITEM_DT = np.dtype([("row", np.uint32), ("gid", np.uint32)])         # rg_send_item_t: send_list
 ORIGIN_NONE, ORIGIN_EXPIRED = 0xFFFFFFFF, 0x80000000      # rg_assembled_t.origin: no event in the cell / bit 31 of the id of an entry of the expired source
+ASM_CARRIED = 0x40000000                                  # origin / deferred id of carry slot c: ASM_CARRIED | c (rg_assembler_carry_enable)
+ROUTE_CARRIED, ROUTE_SPILLED = 0x80000000, 0xFFFFFFFE     # rg_route32_carry: a cell entry of an event deferred into slot (value & 0x3FFFFFFF) of the next carry / one the carry had no room for
+CARRY_NEXT, CARRY_LAST = 0, 1                             # rg_assembler_carry_read: the carry the next run will read / the one the last run read
 EXPIRED_UNTRUSTED = 0xFFFFFFFF                            # *expired_count of a tick whose look-back ran into its bound
 
 

@@ -1102,14 +1102,69 @@ struct rg_assembler {
     enum { RT_GID, RT_WORDS, RT_ORIGIN, RT_ROW, RT_PERSIST, RT_SEND, RT_CELL, RT_OROW, RT_OPERSIST, RT_XCELL, RT_XROW, RT_XPERSIST, RT_PLIST, RT_ALIST, RT_SLIST, RT_SOFF,
            RT_COUNTS, RT_PC, RT_AC, RT_SC, RT_COLUMNS };
     Staging rt[RT_COLUMNS];                         // RG_MEM_HOST: the columns of rg_decided_t and rg_routed_t, and the lists' count arrays
+    // the carry (rg_assembler_carry_enable): two carries in device memory; a run reads carry[runs & 1] and leaves the other: the host's call counter, never device data
+    struct Carry { uint32_t *count = nullptr, *gid = nullptr; rg::U32x2 *head = nullptr; rg::I32x4 *abcd = nullptr; };
+    uint32_t carry_cap = 0;
+    Carry carry[2];
+    unsigned runs = 0;
+    enum { RC_CELL, RC_ROW, RC_PERSIST, RC_COLUMNS };
+    Staging rc[RC_COLUMNS];                         // RG_MEM_HOST: the columns of rg_routed_carry_t
 };
+
+// what an assembler holds per event (and per carried slot): freed, then allocated for max_events + max_expired + carry_capacity positions and two carries of
+// carry_capacity rows (called with the table's device current and its stream idle; on failure the assembler holds none of them)
+static void assembler_release_events(struct rg_assembler *a)
+{
+    rg::AsmParams &p = a->sc;
+    void *cols[] = {p.rowcnt, p.segoff, p.seg, p.flag, p.dcounts, p.big, p.where, a->carry[0].count, a->carry[0].gid, a->carry[0].head, a->carry[0].abcd,
+                    a->carry[1].count, a->carry[1].gid, a->carry[1].head, a->carry[1].abcd};
+    for (void *c : cols) if (c) (void)hipFree(c);
+    p.rowcnt = p.segoff = p.seg = p.dcounts = p.big = p.where = nullptr; p.flag = nullptr;
+    a->carry[0] = a->carry[1] = rg_assembler::Carry{};
+    a->carry_cap = 0; a->runs = 0; a->ran = false;
+}
+
+static int assembler_size_events(struct rg_assembler *a, uint32_t carry_capacity, const char *who)
+{
+    rg_table *t = a->t;
+    assembler_release_events(a);
+    rg::AsmParams &p = a->sc;
+    const size_t G = t->G, events = (size_t)a->max_events + a->max_expired + carry_capacity, eb = events ? (events + 255) / 256 : 1, K = carry_capacity;
+    p.seg_cap = (uint32_t)events;
+    p.rows_cap = (uint32_t)(G < events ? G : events);                  // a listed row has an event: there are never more rows than events, or than groups
+    p.big_cap = (uint32_t)(events / (rg::ASM_SMALL + 1) + 1);          // ... and a row queued for asm_big_rows_kernel has more than ASM_SMALL of them
+    struct { void **ptr; size_t bytes; bool zero; } cols[] = {
+        {(void **)&p.rowcnt, ((size_t)p.rows_cap + 1) * sizeof(uint32_t), false}, {(void **)&p.segoff, ((size_t)p.rows_cap + 1) * sizeof(uint32_t), false},
+        {(void **)&p.seg, (events + 1) * sizeof(uint32_t), false}, {(void **)&p.flag, events + 1, false}, {(void **)&p.dcounts, (eb * 4 + 1) * sizeof(uint32_t), false},
+        {(void **)&p.big, (size_t)p.big_cap * sizeof(uint32_t), false},
+        {(void **)&p.where, K ? (events + 1) * sizeof(uint32_t) : 0, false},
+        {(void **)&a->carry[0].count, K ? sizeof(uint32_t) : 0, true}, {(void **)&a->carry[1].count, K ? sizeof(uint32_t) : 0, true},
+        {(void **)&a->carry[0].gid, K * sizeof(uint32_t), false}, {(void **)&a->carry[1].gid, K * sizeof(uint32_t), false},
+        {(void **)&a->carry[0].head, K * sizeof(rg::U32x2), false}, {(void **)&a->carry[1].head, K * sizeof(rg::U32x2), false},
+        {(void **)&a->carry[0].abcd, K * sizeof(rg::I32x4), false}, {(void **)&a->carry[1].abcd, K * sizeof(rg::I32x4), false}};
+    for (auto &c : cols) {
+        if (!c.bytes) continue;
+        hipError_t e = hipMalloc(c.ptr, c.bytes);
+        if (e == hipSuccess && c.zero) e = hipMemsetAsync(*c.ptr, 0, c.bytes, t->stream);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(t->stream);
+            assembler_release_events(a);
+            return fail(t, -2, "%s: %zu bytes of scratch: %s", who, c.bytes, hipGetErrorString(e));
+        }
+    }
+    if (hipStreamSynchronize(t->stream) != hipSuccess) { assembler_release_events(a); return fail(t, -2, "%s: hipStreamSynchronize failed", who); }
+    a->carry_cap = carry_capacity;
+    return 0;
+}
 
 static void assembler_release(struct rg_assembler *a)
 {
-    void *cols[] = {a->sc.cnt, a->sc.bitmap, a->sc.rowof, a->sc.wordoff, a->sc.rowcnt, a->sc.segoff, a->sc.seg, a->sc.flag, a->sc.dcounts, a->sc.big, a->sc.scalars};
+    assembler_release_events(a);
+    void *cols[] = {a->sc.cnt, a->sc.bitmap, a->sc.rowof, a->sc.wordoff, a->sc.scalars};
     for (void *c : cols) if (c) (void)hipFree(c);
     release(a->as, rg_assembler::AS_COLUMNS);
     release(a->rt, rg_assembler::RT_COLUMNS);
+    release(a->rc, rg_assembler::RC_COLUMNS);
     *a = rg_assembler{};
 }
 
@@ -1137,17 +1192,11 @@ int rg_assembler_create(rg_table_t *t, uint32_t max_events, uint32_t max_expired
     rg_assembler *a = new rg_assembler();
     a->t = t; a->max_events = max_events; a->max_expired = max_expired;
     rg::AsmParams &p = a->sc;
-    const size_t G = t->G, words = (G + 63) / 64, events = (size_t)max_events + max_expired, eb = events ? (events + 255) / 256 : 1;
+    const size_t G = t->G, words = (G + 63) / 64;
     p.groups = t->G; p.words = (uint32_t)words;
-    p.seg_cap = (uint32_t)events;
-    p.rows_cap = (uint32_t)(G < events ? G : events);                  // a listed row has an event: there are never more rows than events, or than groups
-    p.big_cap = (uint32_t)(events / (rg::ASM_SMALL + 1) + 1);          // ... and a row queued for asm_big_rows_kernel has more than ASM_SMALL of them
     struct { void **ptr; size_t bytes; bool zero; } cols[] = {
         {(void **)&p.cnt, G * sizeof(uint32_t), true}, {(void **)&p.bitmap, words * sizeof(unsigned long long), true}, {(void **)&p.rowof, G * sizeof(uint32_t), true},
-        {(void **)&p.wordoff, (words + 1) * sizeof(uint32_t), false}, {(void **)&p.rowcnt, ((size_t)p.rows_cap + 1) * sizeof(uint32_t), false},
-        {(void **)&p.segoff, ((size_t)p.rows_cap + 1) * sizeof(uint32_t), false}, {(void **)&p.seg, (events + 1) * sizeof(uint32_t), false},
-        {(void **)&p.flag, events + 1, false}, {(void **)&p.dcounts, (eb * 4 + 1) * sizeof(uint32_t), false}, {(void **)&p.big, (size_t)p.big_cap * sizeof(uint32_t), false},
-        {(void **)&p.scalars, (rg::ASM_SCALARS + 2) * sizeof(uint32_t), true}};
+        {(void **)&p.wordoff, (words + 1) * sizeof(uint32_t), false}, {(void **)&p.scalars, (rg::ASM_SCALARS + 3) * sizeof(uint32_t), true}};
     for (auto &c : cols) {
         hipError_t e = hipMalloc(c.ptr, c.bytes);
         if (e == hipSuccess && c.zero) e = hipMemsetAsync(*c.ptr, 0, c.bytes, t->stream);
@@ -1157,7 +1206,7 @@ int rg_assembler_create(rg_table_t *t, uint32_t max_events, uint32_t max_expired
             return fail(t, -2, "rg_assembler_create: %zu bytes of scratch: %s", c.bytes, hipGetErrorString(e));
         }
     }
-    if (hipStreamSynchronize(t->stream) != hipSuccess) { assembler_release(a); delete a; return fail(t, -2, "rg_assembler_create: hipStreamSynchronize failed"); }
+    if (int rc = assembler_size_events(a, 0, "rg_assembler_create")) { assembler_release(a); delete a; return rc; }
     t->assemblers.push_back(a);
     *out = a;
     return 0;
@@ -1181,10 +1230,19 @@ int rg_assemble32(rg_assembler_t *a, const rg_arrivals_t *in, const rg_assembled
     if (expired && in->expired_capacity > a->max_expired)
         return fail(t, -1, "%s: an expired source of %u entries, the assembler was created for %u", who, in->expired_capacity, a->max_expired);
     if (memspace != RG_MEM_DEVICE && memspace != RG_MEM_HOST) return fail(t, -1, "%s: unknown memspace %d", who, memspace);
+    if (!a->sc.seg) return fail(t, -1, "%s: the assembler holds no scratch (an rg_assembler_carry_enable ran out of memory): enable again, or destroy it", who);
+    if (a->carry_cap && t->auto_window)
+        return fail(t, -1, "%s: a carrying assembler on a table with RG_OPT_AUTO_INDEX_BASE: a base that a decided row moves would leave the group's carried rows relative to the old one", who);
     const uint32_t C = out->capacity, D = out->max_rounds, ex_cap = expired ? in->expired_capacity : 0u;
     const size_t cells = (size_t)C * D;
     rg::AsmParams p = a->sc;
     p.in_cap = in->capacity; p.ex_cap = ex_cap; p.C = C; p.D = D; p.deferred_cap = out->deferred_capacity;
+    if (a->carry_cap) {                                                // the carry stays in the assembler's device memory in both memspaces
+        const rg_assembler::Carry &rd = a->carry[a->runs & 1u], &wr = a->carry[(a->runs & 1u) ^ 1u];
+        p.carry_cap = a->carry_cap;
+        p.cr_count = rd.count; p.cr_gid = rd.gid; p.cr_head = rd.head; p.cr_abcd = rd.abcd;
+        p.cw_count = wr.count; p.cw_gid = wr.gid; p.cw_head = wr.head; p.cw_abcd = wr.abcd;
+    }
     if (memspace == RG_MEM_DEVICE) {
         void *v[16] = {};
         const struct { const void *ptr; const char *what; } cols[] = {
@@ -1199,7 +1257,7 @@ int rg_assemble32(rg_assembler_t *a, const rg_arrivals_t *in, const rg_assembled
         p.origin = (uint32_t *)v[12]; p.deferred = (uint32_t *)v[13]; p.stats = (uint32_t *)v[14];
         if (bind(t)) return -2;
         HIP_TRY(t, rg::launch_assemble(p, t->stream));
-        a->ran = true; a->last_C = C; a->last_D = D; a->last_in_cap = in->capacity; a->last_ex_cap = ex_cap;
+        a->ran = true; a->last_C = C; a->last_D = D; a->last_in_cap = in->capacity; a->last_ex_cap = ex_cap; a->runs += 1;
         return 0;
     }
     if (bind(t)) return -2;
@@ -1220,7 +1278,7 @@ int rg_assemble32(rg_assembler_t *a, const rg_arrivals_t *in, const rg_assembled
     p.ex_count = expired ? p.in_count + 1 : nullptr;
     p.count = ow; p.rounds = ow + 1; p.stats = ow + 2;
     HIP_TRY(t, rg::launch_assemble(p, s));
-    a->ran = true; a->last_C = C; a->last_D = D; a->last_in_cap = in->capacity; a->last_ex_cap = ex_cap;
+    a->ran = true; a->last_C = C; a->last_D = D; a->last_in_cap = in->capacity; a->last_ex_cap = ex_cap; a->runs += 1;
     uint32_t back[6] = {};
     HIP_TRY(t, hipMemcpyAsync(back, ow, sizeof back, hipMemcpyDeviceToHost, s));
     HIP_TRY(t, hipStreamSynchronize(s));
@@ -1241,12 +1299,19 @@ int rg_assemble32(rg_assembler_t *a, const rg_arrivals_t *in, const rg_assembled
 }
 
 /* ---- routing a decided batch back to arrival order (rg_route32; kernels: rg_route.hpp) ----------------------------------------------- */
-int rg_route32(rg_assembler_t *a, const rg_decided_t *in, const rg_routed_t *out, int memspace)
+// rg_route32 (carried == nullptr) and rg_route32_carry: the same checks, staging and launch_route; the second adds the carried columns and their pass
+static int route32(rg_assembler_t *a, const rg_decided_t *in, const rg_routed_t *out, const rg_routed_carry_t *carried, bool carry, int memspace, const char *who)
 {
     if (!a || !a->t) return -1;
     rg_table *t = a->t;
-    const char *who = "rg_route32";
     if (!in || !out) return fail(t, -1, "%s: NULL decided batch or routed columns", who);
+    if (carry && !a->carry_cap) return fail(t, -1, "%s: the assembler has no carry (rg_assembler_carry_enable)", who);
+    if (carry && (!carried || (carried->capacity && (!carried->cell || !carried->row || !carried->persist32))))
+        return fail(t, -1, "%s: cell, row and persist32 of the carried columns are required", who);
+    if (carry && carried->capacity != a->carry_cap)
+        return fail(t, -1, "%s: a carried capacity of %u, the assembler's carry holds %u", who, carried->capacity, a->carry_cap);
+    if (carry && (uint64_t)in->capacity * in->max_rounds > (1ull << 31))
+        return fail(t, -1, "%s: %u x %u cells: a cell index beside RG_ROUTE_CARRIED holds at most 2^31", who, in->capacity, in->max_rounds);
     if (!in->gid || !in->count || !in->rounds || !in->origin || !in->row || !in->persist32)
         return fail(t, -1, "%s: gid, count, rounds, origin, row and persist32 of the decided batch are required", who);
     if (!out->counts || (out->arrival_capacity && (!out->cell || !out->row || !out->persist32)) || (out->persist_capacity && !out->persist_list) ||
@@ -1277,13 +1342,17 @@ int rg_route32(rg_assembler_t *a, const rg_decided_t *in, const rg_routed_t *out
     p.persist_cap = out->persist_capacity; p.attention_cap = out->attention_capacity; p.send_cap = sends ? out->send_capacity : 0u;
     const size_t W = (size_t)D * p.bpr * 4, Ws = (size_t)F * p.bpr * 4;
     typedef rg_assembler A;
+    rg::RouteCarryParams cp{};
+    cp.last = p.last; cp.where = a->sc.where; cp.in_cap = in_cap; cp.ex_cap = a->last_ex_cap; cp.carry_cap = a->carry_cap; cp.cells = C * D;
     if (memspace == RG_MEM_DEVICE) {
         void *v[24] = {};
         const struct { const void *ptr; const char *what; } cols[] = {
             {in->gid, "gid"}, {in->count, "count"}, {in->rounds, "rounds"}, {in->origin, "origin"}, {in->row, "the decided row"}, {in->persist32, "the decided persist32"},
             {in->send_head, "send_head"}, {in->send, "send"}, {out->cell, "cell"}, {out->row, "the routed row"}, {out->persist32, "the routed persist32"},
             {out->expired_cell, "expired_cell"}, {out->expired_row, "expired_row"}, {out->expired_persist32, "expired_persist32"}, {out->persist_list, "persist_list"},
-            {out->attention, "attention"}, {out->send_list, "send_list"}, {out->send_offset, "send_offset"}, {out->counts, "counts"}};
+            {out->attention, "attention"}, {out->send_list, "send_list"}, {out->send_offset, "send_offset"}, {out->counts, "counts"},
+            {carry ? carried->cell : nullptr, "the carried cell"}, {carry ? carried->row : nullptr, "the carried row"},
+            {carry ? carried->persist32 : nullptr, "the carried persist32"}};
         int k = 0;
         for (const auto &c : cols) if (int rc = device_visible(t, who, c.ptr, c.what, &v[k++])) return rc;
         if (bind(t)) return -2;
@@ -1294,13 +1363,18 @@ int rg_route32(rg_assembler_t *a, const rg_decided_t *in, const rg_routed_t *out
         p.ex_cell = (uint32_t *)v[11]; p.ex_row = (rg::I32x4 *)v[12]; p.ex_persist = (rg::I32x4 *)v[13];
         p.persist_list = (rg::U32x2 *)v[14]; p.attention = (rg::U32x2 *)v[15]; p.send_list = (rg::U32x2 *)v[16]; p.send_offset = (uint32_t *)v[17]; p.counts = (uint32_t *)v[18];
         HIP_TRY(t, rg::launch_route(p, t->stream));
+        if (carry) {
+            cp.row = p.row; cp.persist32 = p.persist32; cp.cell = p.cell; cp.ex_cell = p.ex_cell;
+            cp.cr_cell = (uint32_t *)v[19]; cp.cr_row = (rg::I32x4 *)v[20]; cp.cr_persist = (rg::I32x4 *)v[21];
+            HIP_TRY(t, rg::launch_route_carry(cp, t->stream));
+        }
         return 0;
     }
     if (bind(t)) return -2;
     hipStream_t s = t->stream;
     // host memory: the e and m of the run come back first; then rows 0 .. n - 1 of rounds 0 .. R - 1 go in, and with them what the routed columns hold below m / e — a
     // placed entry is overwritten, any other travels back as it came —; out come the entries below m / e and what the lists hold
-    uint32_t last[2] = {};
+    uint32_t last[3] = {};
     HIP_TRY(t, hipMemcpyAsync(last, a->sc.scalars + rg::ASM_LAST, sizeof last, hipMemcpyDeviceToHost, s));
     HIP_TRY(t, hipStreamSynchronize(s));
     const uint32_t e = expired ? (last[0] < ex_cap ? last[0] : ex_cap) : 0u, m = last[1] < in_cap ? last[1] : in_cap;
@@ -1335,6 +1409,16 @@ int rg_route32(rg_assembler_t *a, const rg_decided_t *in, const rg_routed_t *out
         HIP_TRY(t, col_up(rt[A::RT_XPERSIST], out->expired_persist32, 0, e, s));
     }
     HIP_TRY(t, rg::launch_route(p, s));
+    const uint32_t q = carry ? (last[2] < a->carry_cap ? last[2] : a->carry_cap) : 0u;
+    if (carry) {                                                       // the carried columns: as the arrival columns, entries below q
+        if (stage_out(t, a->rc[A::RC_CELL], (size_t)q + 1, &cp.cr_cell) || stage_out(t, a->rc[A::RC_ROW], (size_t)q + 1, &cp.cr_row) ||
+            stage_out(t, a->rc[A::RC_PERSIST], (size_t)q + 1, &cp.cr_persist))
+            return -2;
+        cp.row = p.row; cp.persist32 = p.persist32; cp.cell = p.cell; cp.ex_cell = p.ex_cell;
+        HIP_TRY(t, col_up(a->rc[A::RC_ROW], carried->row, 0, q, s));
+        HIP_TRY(t, col_up(a->rc[A::RC_PERSIST], carried->persist32, 0, q, s));
+        HIP_TRY(t, rg::launch_route_carry(cp, s));
+    }
     uint32_t counts[4] = {};
     HIP_TRY(t, col_down(rt[A::RT_COUNTS], counts, 0, 4, s));
     HIP_TRY(t, hipStreamSynchronize(s));
@@ -1353,7 +1437,69 @@ int rg_route32(rg_assembler_t *a, const rg_decided_t *in, const rg_routed_t *out
         HIP_TRY(t, col_down(rt[A::RT_SLIST], out->send_list, 0, counts[2] < p.send_cap ? counts[2] : p.send_cap, s));
         HIP_TRY(t, col_down(rt[A::RT_SOFF], out->send_offset, 0, (size_t)F + 1, s));
     }
+    if (carry) {
+        HIP_TRY(t, col_down(a->rc[A::RC_CELL], carried->cell, 0, q, s));
+        HIP_TRY(t, col_down(a->rc[A::RC_ROW], carried->row, 0, q, s));
+        HIP_TRY(t, col_down(a->rc[A::RC_PERSIST], carried->persist32, 0, q, s));
+    }
     HIP_TRY(t, hipStreamSynchronize(s));
+    return 0;
+}
+
+int rg_route32(rg_assembler_t *a, const rg_decided_t *in, const rg_routed_t *out, int memspace) { return route32(a, in, out, nullptr, false, memspace, "rg_route32"); }
+
+int rg_route32_carry(rg_assembler_t *a, const rg_decided_t *in, const rg_routed_t *out, const rg_routed_carry_t *carried, int memspace)
+{
+    return route32(a, in, out, carried, true, memspace, "rg_route32_carry");
+}
+
+/* ---- the carry of an assembler (include/raftgpu.h, "carrying deferred events") -------------------------------------------------------- */
+int rg_assembler_carry_enable(rg_assembler_t *a, uint32_t carry_capacity)
+{
+    if (!a || !a->t) return -1;
+    rg_table *t = a->t;
+    const char *who = "rg_assembler_carry_enable";
+    if (carry_capacity && (a->max_events >= (1u << 30) || a->max_expired >= (1u << 30) || carry_capacity >= (1u << 30)))
+        return fail(t, -1, "%s: max_events %u, max_expired %u, carry_capacity %u: each stays below 2^30 (the ids of carried slots carry bit 30)", who, a->max_events,
+                    a->max_expired, carry_capacity);
+    if (bind(t)) return -2;
+    HIP_TRY(t, hipStreamSynchronize(t->stream));
+    return assembler_size_events(a, carry_capacity, who);
+}
+
+int rg_assembler_carry_reset(rg_assembler_t *a)
+{
+    if (!a || !a->t) return -1;
+    rg_table *t = a->t;
+    if (!a->carry_cap) return fail(t, -1, "rg_assembler_carry_reset: the assembler has no carry (rg_assembler_carry_enable)");
+    if (bind(t)) return -2;
+    HIP_TRY(t, hipMemsetAsync(a->carry[a->runs & 1u].count, 0, sizeof(uint32_t), t->stream));
+    return 0;
+}
+
+int rg_assembler_carry_read(rg_assembler_t *a, int which, uint32_t capacity, uint32_t *count, uint32_t *gid, rg_ev_head_t *head, rg_ev_quad32_t *abcd)
+{
+    if (!a || !a->t) return -1;
+    rg_table *t = a->t;
+    const char *who = "rg_assembler_carry_read";
+    if (!a->carry_cap) return fail(t, -1, "%s: the assembler has no carry (rg_assembler_carry_enable)", who);
+    if (which != RG_CARRY_NEXT && which != RG_CARRY_LAST) return fail(t, -1, "%s: unknown carry %d", who, which);
+    if (!count || (capacity && (!gid || !head || !abcd))) return fail(t, -1, "%s: count is required (and gid, head and abcd, unless capacity is 0)", who);
+    if (bind(t)) return -2;
+    const rg_assembler::Carry &c = a->carry[(a->runs & 1u) ^ (which == RG_CARRY_LAST ? 1u : 0u)];
+    hipStream_t s = t->stream;
+    uint32_t q = 0;
+    HIP_TRY(t, hipMemcpyAsync(&q, c.count, sizeof q, hipMemcpyDeviceToHost, s));
+    HIP_TRY(t, hipStreamSynchronize(s));
+    q = q < a->carry_cap ? q : a->carry_cap;
+    *count = q;
+    const size_t k = q < capacity ? q : capacity;
+    if (k) {
+        HIP_TRY(t, hipMemcpyAsync(gid, c.gid, k * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(t, hipMemcpyAsync(head, c.head, k * sizeof(rg_ev_head_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(t, hipMemcpyAsync(abcd, c.abcd, k * sizeof(rg_ev_quad32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(t, hipStreamSynchronize(s));
+    }
     return 0;
 }
 

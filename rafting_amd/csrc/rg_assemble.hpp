@@ -20,6 +20,17 @@
 //   7. asm_defer_count / timers_scan_kernel / asm_defer_emit: the flagged positions compacted in S order; the last kernel also writes stats and puts back what the
 //                           run touched of the scratch: cnt and the bitmap word of every event's group, the scalars — and remembers e and m for rg_route32. The cost of a run follows m + e and groups / 64
 //                           (steps 2, 3), never groups x anything.
+//
+// THE CARRY (rg_assembler_carry_enable; off: everything above, unchanged). A carrying assembler owns two carries of carry_cap complete rows (gid, head, abcd) and a
+// count each. A run reads one of them as a THIRD source, between the other two — S = the e fired tickets, the q carried slots (position e + c, id 0x40000000 | c),
+// the m arrivals (position e + q + k) — and leaves the events it deferred, in S order, in the other: which is which is the host's call counter, q is read on the
+// device. The carrying run is the same ten launches over kernels of its own (asm_*_carry_kernel: the bodies below with the third source compiled in; the plain
+// kernels are the bodies with it compiled out) and an eleventh:
+//   8. asm_carry_gather_kernel  per position: a deferred event — the p-th of the run's deferred sequence, what deferred[p] names — is stored as a complete row in slot
+//                           p of the other carry while p < carry_cap (a fired ticket as the RG_EV_TIMEOUT row asm_put would have made of it); one lane writes that
+//                           carry's count. It also leaves rg_route32_carry, per position, where the event went (`where`: 0x80000000 | slot, 0xFFFFFFFE for one
+//                           the carry had no room for, 0xFFFFFFFF for any other event that is not a carried one; the cell of a carried event that was placed is
+//                           stored by asm_put).
 #pragma once
 
 #include "rg_device.hpp"
@@ -30,6 +41,8 @@ constexpr uint32_t ASM_SMALL = 64;              // a row with at most this many 
 constexpr uint32_t ASM_BIG_BLOCKS = 256;        // workgroups that share the rows with more
 constexpr uint32_t ASM_POOL = 0, ASM_N_BIG = 1, ASM_BAD = 2, ASM_MARK = 3, ASM_SCALARS = ASM_MARK + 65, ASM_LAST = ASM_SCALARS;     // the scratch words `scalars`
 constexpr uint32_t ASM_EXPIRED_ID = 0x80000000u, ASM_NO_EVENT = 0xFFFFFFFFu;
+constexpr uint32_t ASM_CARRIED_ID = 0x40000000u;  // RG_ASM_CARRIED
+constexpr uint32_t ASM_WENT_CARRIED = 0x80000000u, ASM_WENT_SPILLED = 0xFFFFFFFEu, ASM_WENT_NOWHERE = 0xFFFFFFFFu;   // `where`: RG_ROUTE_CARRIED, RG_ROUTE_SPILLED, RG_ROUTE_NONE
 
 struct AsmParams {
     // the arrival log and the optional list of fired tickets (rg_arrivals_t)
@@ -55,16 +68,27 @@ struct AsmParams {
     uint8_t *flag;                                  // [seg_cap] per position: 1 = deferred
     uint32_t *dcounts;                              // [4 * event workgroups + 1] per-wavefront counts of deferred positions -> offsets, last = their sum
     uint32_t *big;                                  // [big_cap] rows with more than ASM_SMALL events
-    uint32_t *scalars;                              // [ASM_SCALARS] 0 between runs, + [ASM_LAST .. ASM_LAST + 2) the e and m the last run read, kept for rg_route32 (rg_route.hpp)
+    uint32_t *scalars;                              // [ASM_SCALARS] 0 between runs, + [ASM_LAST .. ASM_LAST + 3) the e, m and q the last run read, kept for rg_route32 (rg_route.hpp)
     uint32_t rows_cap, seg_cap, big_cap;
+    // the carry (cr_count == nullptr: an assembler without one, and the plain kernels, which never read these)
+    uint32_t carry_cap;
+    const uint32_t *cr_count, *cr_gid;              // the carry this run reads: [1] = q, [carry_cap] rows
+    const U32x2 *cr_head;
+    const I32x4 *cr_abcd;
+    uint32_t *cw_count, *cw_gid;                    // the carry it leaves
+    U32x2 *cw_head;
+    I32x4 *cw_abcd;
+    uint32_t *where;                                // [seg_cap] per position: where the event went, for rg_route32_carry (asm_carry_gather_kernel)
 };
 
 hipError_t launch_assemble(const AsmParams &p, hipStream_t s);
 
 #ifdef RG_ASSEMBLE_KERNELS
 
-struct AsmRun { uint32_t e, m, T; };
+// K: the third source, the carry, is compiled in (the kernels of a carrying run) or out (q = 0 at compile time: the plain kernels)
+struct AsmRun { uint32_t e, q, m, T; };
 
+template <bool K>
 __device__ __forceinline__ AsmRun asm_run(const AsmParams &p)
 {
     AsmRun r;
@@ -73,34 +97,58 @@ __device__ __forceinline__ AsmRun asm_run(const AsmParams &p)
         const uint32_t c = *p.ex_count;             // 0xFFFFFFFF: the tick's look-back ran into its bound, the list is not to be trusted (tick_fold_kernel)
         r.e = c == 0xFFFFFFFFu ? 0u : (c < p.ex_cap ? c : p.ex_cap);
     }
+    r.q = 0;
+    if constexpr (K) {
+        const uint32_t c = *p.cr_count;
+        r.q = c < p.carry_cap ? c : p.carry_cap;
+    }
     const uint32_t c = *p.in_count;
     r.m = c < p.in_cap ? c : p.in_cap;
-    r.T = r.e + r.m;
+    r.T = r.e + r.q + r.m;
     return r;
 }
-__device__ __forceinline__ uint32_t asm_gid(const AsmParams &p, const AsmRun &r, uint32_t s) { return s < r.e ? p.ex_gid[s] : p.in_gid[s - r.e]; }
-__device__ __forceinline__ uint32_t asm_id(const AsmRun &r, uint32_t s) { return s < r.e ? (ASM_EXPIRED_ID | s) : s - r.e; }
+template <bool K>
+__device__ __forceinline__ uint32_t asm_gid(const AsmParams &p, const AsmRun &r, uint32_t s)
+{
+    if (s < r.e) return p.ex_gid[s];
+    if constexpr (K) { if (s - r.e < r.q) return p.cr_gid[s - r.e]; }
+    return p.in_gid[s - r.e - r.q];
+}
+template <bool K>
+__device__ __forceinline__ uint32_t asm_id(const AsmRun &r, uint32_t s)
+{
+    if (s < r.e) return ASM_EXPIRED_ID | s;
+    if constexpr (K) { if (s - r.e < r.q) return ASM_CARRIED_ID | (s - r.e); }
+    return s - r.e - r.q;
+}
 
-// the event at position s into cell (round, row): a fired ticket becomes its fenced RG_EV_TIMEOUT row, an arrival moves verbatim (8-byte and 16-byte accesses)
+// the event at position s into cell (round, row): a fired ticket becomes its fenced RG_EV_TIMEOUT row, a carried slot and an arrival move verbatim (8-byte and
+// 16-byte accesses); a carried slot leaves the route its cell
+template <bool K>
 __device__ __forceinline__ void asm_put(const AsmParams &p, const AsmRun &r, uint32_t round, uint32_t row, uint32_t s)
 {
     const size_t cell = (size_t)round * p.C + row;
     if (s < r.e) {
         p.head[cell] = U32x2{RG_HDR_MAKE(RG_EV_TIMEOUT, 0, 0, 0), p.ex_epoch[s]};
         p.abcd[cell] = I32x4{0, 0, 0, 0};
+    } else if (K && s - r.e < r.q) {
+        p.head[cell] = p.cr_head[s - r.e];
+        p.abcd[cell] = p.cr_abcd[s - r.e];
+        p.where[s] = (uint32_t)cell;
     } else {
-        p.head[cell] = p.in_head[s - r.e];
-        p.abcd[cell] = p.in_abcd[s - r.e];
+        p.head[cell] = p.in_head[s - r.e - r.q];
+        p.abcd[cell] = p.in_abcd[s - r.e - r.q];
     }
-    p.origin[cell] = asm_id(r, s);
+    p.origin[cell] = asm_id<K>(r, s);
 }
 
-__global__ __launch_bounds__(256) void asm_mark_kernel(const AsmParams p)
+template <bool K>
+__device__ __forceinline__ void asm_mark_body(const AsmParams &p)
 {
-    const AsmRun r = asm_run(p);
+    const AsmRun r = asm_run<K>(p);
     const uint32_t s = blockIdx.x * 256u + threadIdx.x;
     const bool live = s < r.T;
-    const uint32_t g = live ? asm_gid(p, r, s) : 0u;
+    const uint32_t g = live ? asm_gid<K>(p, r, s) : 0u;
     const bool bad = live && g >= p.groups;
     const unsigned long long mb = __ballot(bad);
     if (mb != 0ull && (threadIdx.x & 63u) == 0u) atomicAdd(&p.scalars[ASM_BAD], (uint32_t)__popcll(mb));
@@ -109,6 +157,8 @@ __global__ __launch_bounds__(256) void asm_mark_kernel(const AsmParams p)
     if (bad) return;
     if (atomicAdd(&p.cnt[g], 1u) == 0u) atomicAdd(&p.bitmap[g >> 6], 1ull << (g & 63u));
 }
+__global__ __launch_bounds__(256) void asm_mark_kernel(const AsmParams p) { asm_mark_body<false>(p); }
+__global__ __launch_bounds__(256) void asm_mark_carry_kernel(const AsmParams p) { asm_mark_body<true>(p); }
 
 __global__ __launch_bounds__(256) void asm_words_kernel(const AsmParams p)
 {
@@ -143,9 +193,10 @@ __global__ __launch_bounds__(256) void asm_rows_kernel(const AsmParams p)
     if (listed && row < p.rows_cap) { p.gid[row] = g; p.rowcnt[row] = c; p.segoff[row] = base + before; }
 }
 
-__global__ __launch_bounds__(256) void asm_claim_kernel(const AsmParams p)
+template <bool K>
+__device__ __forceinline__ void asm_claim_body(const AsmParams &p)
 {
-    const AsmRun r = asm_run(p);
+    const AsmRun r = asm_run<K>(p);
     const uint32_t s = blockIdx.x * 256u + threadIdx.x;
     if (s == 0u) {
         uint32_t R = 1u;
@@ -153,20 +204,23 @@ __global__ __launch_bounds__(256) void asm_claim_kernel(const AsmParams p)
         *p.rounds = R;
     }
     if (s >= r.T) return;
-    const uint32_t g = asm_gid(p, r, s);
+    const uint32_t g = asm_gid<K>(p, r, s);
     if (g >= p.groups) return;
     const uint32_t row = p.rowof[g];
     if (row >= p.C || row >= p.rows_cap) { p.flag[s] = 1; return; }
     const uint32_t at = p.segoff[row] + atomicAdd(&p.cnt[g], 1u);
     if (at < p.seg_cap) p.seg[at] = s;
 }
+__global__ __launch_bounds__(256) void asm_claim_kernel(const AsmParams p) { asm_claim_body<false>(p); }
+__global__ __launch_bounds__(256) void asm_claim_carry_kernel(const AsmParams p) { asm_claim_body<true>(p); }
 
-__global__ __launch_bounds__(256) void asm_order_kernel(const AsmParams p)
+template <bool K>
+__device__ __forceinline__ void asm_order_body(const AsmParams &p)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     const uint32_t n = *p.count, R = *p.rounds;
     if (i >= n) return;
-    const AsmRun r = asm_run(p);
+    const AsmRun r = asm_run<K>(p);
     const uint32_t c = p.rowcnt[i], off = p.segoff[i];
     if (c > ASM_SMALL) {
         const uint32_t at = atomicAdd(&p.scalars[ASM_N_BIG], 1u);
@@ -178,7 +232,7 @@ __global__ __launch_bounds__(256) void asm_order_kernel(const AsmParams p)
         if (key >= r.T) continue;                   // (cannot happen while the sources stand still during a run; a caller that breaks that gets wrong rows, not wild stores)
         uint32_t rank = 0;
         for (uint32_t k = 0; k < c; k++) rank += p.seg[off + k] < key ? 1u : 0u;
-        if (rank < p.D) asm_put(p, r, rank, i, key); else p.flag[key] = 1;
+        if (rank < p.D) asm_put<K>(p, r, rank, i, key); else p.flag[key] = 1;
     }
     for (uint32_t q = c < p.D ? c : p.D; q < R; q++) {
         const size_t cell = (size_t)q * p.C + i;
@@ -187,13 +241,16 @@ __global__ __launch_bounds__(256) void asm_order_kernel(const AsmParams p)
         p.origin[cell] = ASM_NO_EVENT;
     }
 }
+__global__ __launch_bounds__(256) void asm_order_kernel(const AsmParams p) { asm_order_body<false>(p); }
+__global__ __launch_bounds__(256) void asm_order_carry_kernel(const AsmParams p) { asm_order_body<true>(p); }
 
-__global__ __launch_bounds__(256) void asm_big_rows_kernel(const AsmParams p)
+template <bool K>
+__device__ __forceinline__ void asm_big_rows_body(const AsmParams &p)
 {
     __shared__ uint32_t hist[256];
     __shared__ uint32_t sel[64];
     __shared__ uint32_t st[3];                      // the prefix of the D-th smallest position found so far, how many-th it is among those that share it, positions selected
-    const AsmRun r = asm_run(p);
+    const AsmRun r = asm_run<K>(p);
     const uint32_t tid = threadIdx.x;
     uint32_t rows = p.scalars[ASM_N_BIG];
     rows = rows < p.big_cap ? rows : p.big_cap;
@@ -237,44 +294,113 @@ __global__ __launch_bounds__(256) void asm_big_rows_kernel(const AsmParams p)
             const uint32_t key = sel[tid];
             uint32_t rank = 0;
             for (uint32_t k = 0; k < p.D; k++) rank += sel[k] < key ? 1u : 0u;
-            if (key < r.T && tid < st[2]) asm_put(p, r, rank, i, key);
+            if (key < r.T && tid < st[2]) asm_put<K>(p, r, rank, i, key);
         }
         __syncthreads();
     }
 }
+__global__ __launch_bounds__(256) void asm_big_rows_kernel(const AsmParams p) { asm_big_rows_body<false>(p); }
+__global__ __launch_bounds__(256) void asm_big_rows_carry_kernel(const AsmParams p) { asm_big_rows_body<true>(p); }
 
-__global__ __launch_bounds__(256) void asm_defer_count_kernel(const AsmParams p)
+template <bool K>
+__device__ __forceinline__ void asm_defer_count_body(const AsmParams &p)
 {
-    const AsmRun r = asm_run(p);
+    const AsmRun r = asm_run<K>(p);
     const uint32_t s = blockIdx.x * 256u + threadIdx.x;
     const unsigned long long m = __ballot(s < r.T && p.flag[s] != 0);
     if ((threadIdx.x & 63u) == 0u) p.dcounts[s >> 6] = (uint32_t)__popcll(m);
 }
+__global__ __launch_bounds__(256) void asm_defer_count_kernel(const AsmParams p) { asm_defer_count_body<false>(p); }
+__global__ __launch_bounds__(256) void asm_defer_count_carry_kernel(const AsmParams p) { asm_defer_count_body<true>(p); }
 
-__global__ __launch_bounds__(256) void asm_defer_emit_kernel(const AsmParams p)
+template <bool K>
+__device__ __forceinline__ void asm_defer_emit_body(const AsmParams &p)
 {
-    const AsmRun r = asm_run(p);
+    const AsmRun r = asm_run<K>(p);
     const uint32_t s = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u;
     const bool live = s < r.T;
     const bool def = live && p.flag[s] != 0;
     const unsigned long long m = __ballot(def);
     if (def) {
         const uint32_t pos = p.dcounts[s >> 6] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-        if (pos < p.deferred_cap) p.deferred[pos] = asm_id(r, s);
+        if (pos < p.deferred_cap) p.deferred[pos] = asm_id<K>(r, s);
     }
     if (s == 0u) {
         const uint32_t deferred = p.dcounts[gridDim.x * 4u], bad = p.scalars[ASM_BAD];
         p.stats[0] = r.T - bad - deferred; p.stats[1] = deferred; p.stats[2] = bad; p.stats[3] = 0u;
         for (uint32_t k = 0; k < ASM_SCALARS; k++) p.scalars[k] = 0u;
         p.scalars[ASM_LAST] = r.e; p.scalars[ASM_LAST + 1u] = r.m;
+        if constexpr (K) {                          // the spilled events: deferred, and beyond what the next carry holds
+            p.stats[3] = deferred > p.carry_cap ? deferred - p.carry_cap : 0u;
+            p.scalars[ASM_LAST + 2u] = r.q;
+        }
     }
     if (!live) return;
-    const uint32_t g = asm_gid(p, r, s);            // the scratch this run touched, back to 0 (every event of a group stores the same)
+    const uint32_t g = asm_gid<K>(p, r, s);            // the scratch this run touched, back to 0 (every event of a group stores the same)
     if (g < p.groups) { p.cnt[g] = 0u; p.bitmap[g >> 6] = 0ull; }
+}
+__global__ __launch_bounds__(256) void asm_defer_emit_kernel(const AsmParams p) { asm_defer_emit_body<false>(p); }
+__global__ __launch_bounds__(256) void asm_defer_emit_carry_kernel(const AsmParams p) { asm_defer_emit_body<true>(p); }
+
+// the deferred events of a carrying run, in S order, into the carry the next run reads; and where every event of the run went, for rg_route32_carry
+__global__ __launch_bounds__(256) void asm_carry_gather_kernel(const AsmParams p)
+{
+    const AsmRun r = asm_run<true>(p);
+    const uint32_t s = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u;
+    const bool live = s < r.T;
+    const bool def = live && p.flag[s] != 0;
+    const unsigned long long m = __ballot(def);
+    if (s == 0u) {
+        const uint32_t deferred = p.dcounts[gridDim.x * 4u];
+        *p.cw_count = deferred < p.carry_cap ? deferred : p.carry_cap;
+    }
+    if (!live) return;
+    const bool carried = s >= r.e && s - r.e < r.q;
+    if (!def) {
+        if (!carried) p.where[s] = ASM_WENT_NOWHERE;        // (a placed carried slot: asm_put stored its cell)
+        return;
+    }
+    const uint32_t pos = p.dcounts[s >> 6] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    if (pos >= p.carry_cap) { p.where[s] = ASM_WENT_SPILLED; return; }
+    p.where[s] = ASM_WENT_CARRIED | pos;
+    if (s < r.e) {
+        p.cw_gid[pos] = p.ex_gid[s];
+        p.cw_head[pos] = U32x2{RG_HDR_MAKE(RG_EV_TIMEOUT, 0, 0, 0), p.ex_epoch[s]};
+        p.cw_abcd[pos] = I32x4{0, 0, 0, 0};
+    } else if (carried) {
+        p.cw_gid[pos] = p.cr_gid[s - r.e];
+        p.cw_head[pos] = p.cr_head[s - r.e];
+        p.cw_abcd[pos] = p.cr_abcd[s - r.e];
+    } else {
+        p.cw_gid[pos] = p.in_gid[s - r.e - r.q];
+        p.cw_head[pos] = p.in_head[s - r.e - r.q];
+        p.cw_abcd[pos] = p.in_abcd[s - r.e - r.q];
+    }
+}
+
+// a carrying run: the same chain over the kernels that read the third source, and the gather behind it
+static hipError_t launch_assemble_carry(const AsmParams &p, hipStream_t s)
+{
+    const uint32_t events = p.in_cap + p.ex_cap + p.carry_cap;
+    const uint32_t eb = events ? (events + 255u) / 256u : 1u;
+    hipLaunchKernelGGL(asm_mark_carry_kernel, dim3(eb), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(asm_words_kernel, dim3((p.words + 255u) / 256u), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(timers_scan_kernel, dim3(1), dim3(1024), 0, s, p.wordoff, p.words, p.wordoff + p.words);
+    hipLaunchKernelGGL(asm_rows_kernel, dim3((p.words * 64u + 255u) / 256u), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(asm_claim_carry_kernel, dim3(eb), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(asm_order_carry_kernel, dim3((p.C + 255u) / 256u), dim3(256), 0, s, p);
+    const uint32_t big = events / (ASM_SMALL + 1u) + 1u;
+    hipLaunchKernelGGL(asm_big_rows_carry_kernel, dim3(big < ASM_BIG_BLOCKS ? big : ASM_BIG_BLOCKS), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(asm_defer_count_carry_kernel, dim3(eb), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(timers_scan_kernel, dim3(1), dim3(1024), 0, s, p.dcounts, eb * 4u, p.dcounts + eb * 4u);
+    hipLaunchKernelGGL(asm_defer_emit_carry_kernel, dim3(eb), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(asm_carry_gather_kernel, dim3(eb), dim3(256), 0, s, p);
+    return hipGetLastError();
 }
 
 hipError_t launch_assemble(const AsmParams &p, hipStream_t s)
 {
+    if (p.cr_count) return launch_assemble_carry(p, s);
     const uint32_t events = p.in_cap + p.ex_cap;
     const uint32_t eb = events ? (events + 255u) / 256u : 1u;       // (the grids cover the capacities; one workgroup at least: it writes count, rounds and stats)
     hipLaunchKernelGGL(asm_mark_kernel, dim3(eb), dim3(256), 0, s, p);

@@ -18,6 +18,13 @@
 //   4. route_emit_kernel        per cell: {cell, gid} into persist_list / attention below their capacities; one lane writes counts
 //   5. route_send_count_kernel / timers_scan_kernel / route_send_emit_kernel: per (follower, row < n) of the send table, the rows whose kind is a send, compacted
 //                               follower-major; the first lane of a follower's first workgroup writes send_offset
+//
+// rg_route32_carry (a carrying assembler, rg_assemble.hpp): launch_route as it is — an id with bit 30 set lies at or above any m, the scatter routes it nowhere —
+// and one more launch behind it over the positions of the run, sized from the three capacities:
+//   6. route_carry_kernel       per position of S, from the word asm_put / asm_carry_gather_kernel left for it (`where`): a fired ticket or an arrival that was
+//                               deferred gets RG_ROUTE_CARRIED | slot or RG_ROUTE_SPILLED over the RG_ROUTE_NONE of step 1; a carried slot c < q gets its entry of
+//                               the carried columns — the same word, or the cell it was placed in, and then that cell's row and, under RG_F_PERSIST, persist row.
+//                               Every destination is written by the one lane that owns the position
 #pragma once
 
 #include "rg_device.hpp"
@@ -50,6 +57,18 @@ struct RouteParams {
 };
 
 hipError_t launch_route(const RouteParams &p, hipStream_t s);
+
+struct RouteCarryParams {
+    const uint32_t *last;                           // {e, m, q} of the assembler's last run
+    const uint32_t *where;                          // [positions of that run] (AsmParams::where)
+    uint32_t in_cap, ex_cap, carry_cap, cells;      // cells = C * D
+    const I32x4 *row, *persist32;                   // [D][C]
+    uint32_t *cell, *ex_cell;                       // the routed cell columns (ex_cell == nullptr: no expired columns)
+    uint32_t *cr_cell;                              // rg_routed_carry_t, [carry_cap]
+    I32x4 *cr_row, *cr_persist;
+};
+
+hipError_t launch_route_carry(const RouteCarryParams &p, hipStream_t s);
 
 // the span of a shape: the smallest that keeps the longest count array — max(D, F) * ceil(C / (4 * span)) * 4 words — within ROUTE_SCAN_WORDS
 inline uint32_t route_span(uint32_t C, uint32_t D, uint32_t F)
@@ -209,6 +228,38 @@ hipError_t launch_route(const RouteParams &p, hipStream_t s)
         hipLaunchKernelGGL(timers_scan_kernel, dim3(1), dim3(1024), 0, s, p.sc, Ws, p.sc + Ws);
         hipLaunchKernelGGL(route_send_emit_kernel, dim3(rows), dim3(256), 0, s, p);
     }
+    return hipGetLastError();
+}
+
+__global__ __launch_bounds__(256) void route_carry_kernel(const RouteCarryParams p)
+{
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x, e = p.last[0], m = p.last[1], q = p.last[2];
+    if (t < p.ex_cap) {
+        if (t >= e || !p.ex_cell) return;
+        const uint32_t w = p.where[t];
+        if (w != ROUTE_NONE) p.ex_cell[t] = w;
+    } else if (t - p.ex_cap < p.carry_cap) {
+        const uint32_t c = t - p.ex_cap;
+        if (c >= q) return;
+        const uint32_t w = p.where[e + c];
+        p.cr_cell[c] = w;
+        if (w < p.cells) {
+            const I32x4 v = p.row[w];
+            p.cr_row[c] = v;
+            if ((uint32_t)v.y & RG_F_PERSIST) p.cr_persist[c] = p.persist32[w];
+        }
+    } else if (t - p.ex_cap - p.carry_cap < p.in_cap) {
+        const uint32_t k = t - p.ex_cap - p.carry_cap;
+        if (k >= m) return;
+        const uint32_t w = p.where[e + q + k];
+        if (w != ROUTE_NONE) p.cell[k] = w;
+    }
+}
+
+hipError_t launch_route_carry(const RouteCarryParams &p, hipStream_t s)
+{
+    const uint32_t events = p.in_cap + p.ex_cap + p.carry_cap;
+    hipLaunchKernelGGL(route_carry_kernel, dim3(events ? (events + 255u) / 256u : 1u), dim3(256), 0, s, p);
     return hipGetLastError();
 }
 

@@ -31,7 +31,7 @@ def exported_symbols():
     """Every entry point include/raftgpu.h declares."""
     return [
         "rg_abi_version", "rg_table_create", "rg_table_destroy", "rg_last_error", "rg_table_groups",
-        "rg_table_cluster", "rg_table_option", "rg_load_state", "rg_read_state", "rg_submit", "rg_submit32", "rg_submit32c", "rg_submit32c_sparse", "rg_submit32c_sparse_rounds", "rg_outcome32_unpack", "rg_outcome32_unpack_rel", "rg_index_base_set", "rg_index_base_get", "rg_index_base_advance", "rg_index_base_advance32", "rg_batch32_pack_rel", "rg_batch32_pack", "rg_submit_async", "rg_submit_async_packed", "rg_submit_wait", "rg_tick_create", "rg_tick_launch", "rg_tick_wait", "rg_tick_destroy", "rg_tick2_create", "rg_tick2_create_sparse", "rg_tick2_create_sparse_rounds", "rg_tick2_launch", "rg_tick2_wait", "rg_tick2_destroy", "rg_assembler_create", "rg_assemble32", "rg_assembler_destroy", "rg_route32", "rg_timers_update32", "rg_health_update32", "rg_sync", "rg_step_kernel", "rg_host_alloc", "rg_host_free", "rg_dev_alloc",
+        "rg_table_cluster", "rg_table_option", "rg_load_state", "rg_read_state", "rg_submit", "rg_submit32", "rg_submit32c", "rg_submit32c_sparse", "rg_submit32c_sparse_rounds", "rg_outcome32_unpack", "rg_outcome32_unpack_rel", "rg_index_base_set", "rg_index_base_get", "rg_index_base_advance", "rg_index_base_advance32", "rg_batch32_pack_rel", "rg_batch32_pack", "rg_submit_async", "rg_submit_async_packed", "rg_submit_wait", "rg_tick_create", "rg_tick_launch", "rg_tick_wait", "rg_tick_destroy", "rg_tick2_create", "rg_tick2_create_sparse", "rg_tick2_create_sparse_rounds", "rg_tick2_launch", "rg_tick2_wait", "rg_tick2_destroy", "rg_assembler_create", "rg_assemble32", "rg_assembler_destroy", "rg_route32", "rg_assembler_carry_enable", "rg_assembler_carry_reset", "rg_assembler_carry_read", "rg_route32_carry", "rg_timers_update32", "rg_health_update32", "rg_sync", "rg_step_kernel", "rg_host_alloc", "rg_host_free", "rg_dev_alloc",
         "rg_dev_free", "rg_copy_to_device", "rg_copy_to_host", "rg_stream", "rg_replicate", "rg_timers_configure", "rg_timers_update",
         "rg_timers_expired", "rg_timers_expired_epochs", "rg_timers_arm", "rg_timers_read", "rg_health_update", "rg_health_failure", "rg_ready", "rg_health_read", "rg_in_flight_read", "rg_in_flight_set",
         "rg_timing_enable",
@@ -135,6 +135,10 @@ def lib():
         L.rg_assemble32.argtypes = [vp, C.POINTER(abi.CArrivals), C.POINTER(abi.CAssembled), i32]
         L.rg_assembler_destroy.argtypes = [vp]
         L.rg_route32.argtypes = [vp, C.POINTER(abi.CDecided), C.POINTER(abi.CRouted), i32]
+        L.rg_assembler_carry_enable.argtypes = [vp, u32]
+        L.rg_assembler_carry_reset.argtypes = [vp]
+        L.rg_assembler_carry_read.argtypes = [vp, i32, u32, C.POINTER(u32), vp, vp, vp]
+        L.rg_route32_carry.argtypes = [vp, C.POINTER(abi.CDecided), C.POINTER(abi.CRouted), C.POINTER(abi.CRoutedCarry), i32]
         L.rg_timers_update32.argtypes = [vp, u32, vp, vp, vp, i32]
         L.rg_health_update32.argtypes = [vp, u32, vp, vp, vp, i32]
         L.rg_replicate.argtypes = [vp, u32, vp, vp, vp, vp, vp, i32]
@@ -545,11 +549,29 @@ class Assembler:
     device. assemble() is the RG_MEM_HOST form on numpy arrays; run_device() queues one RG_MEM_DEVICE run on the table's stream from two structs whose pointers are
     device-visible (abi.CArrivals / abi.CAssembled — for instance over the columns of a Tick2 recorded with sparse_rounds=True: for_tick())."""
 
-    def __init__(self, table, max_events, max_expired=0):
-        self.table, self.max_events, self.max_expired = table, int(max_events), int(max_expired)
+    def __init__(self, table, max_events, max_expired=0, carry=0):
+        self.table, self.max_events, self.max_expired, self.carry = table, int(max_events), int(max_expired), 0
         h = C.c_void_p()
         table._check(lib().rg_assembler_create(table._h, self.max_events, self.max_expired, C.byref(h)))
         self._h = h
+        if carry:
+            self.carry_enable(carry)
+
+    def carry_enable(self, capacity):
+        """rg_assembler_carry_enable: the assembler keeps up to `capacity` deferred events for its next run (0: no carry); empties the carry"""
+        self.table._check(lib().rg_assembler_carry_enable(self._h, int(capacity)))
+        self.carry = int(capacity)
+
+    def carry_reset(self):
+        """rg_assembler_carry_reset: the next run reads an empty carry (asynchronous on the table's stream)"""
+        self.table._check(lib().rg_assembler_carry_reset(self._h))
+
+    def carry_read(self, which=abi.CARRY_NEXT):
+        """rg_assembler_carry_read -> (gid, head, abcd) of the slots of the carry the next run will read (abi.CARRY_NEXT) or the last run read (abi.CARRY_LAST)"""
+        k = max(self.carry, 1)
+        n, gid, head, abcd = C.c_uint32(0), np.zeros(k, np.uint32), np.zeros(k, abi.HEAD_DT), np.zeros(k, abi.QUAD32_DT)
+        self.table._check(lib().rg_assembler_carry_read(self._h, int(which), self.carry, C.byref(n), gid.ctypes.data, head.ctypes.data, abcd.ctypes.data))
+        return gid[: n.value], head[: n.value], abcd[: n.value]
 
     def run_device(self, arrivals, assembled):
         self.table._check(lib().rg_assemble32(self._h, C.byref(arrivals), C.byref(assembled), abi.MEM_DEVICE))
@@ -561,7 +583,7 @@ class Assembler:
         gid = np.ascontiguousarray(gid, dtype=np.uint32)
         head, abcd = np.ascontiguousarray(head, dtype=abi.HEAD_DT), np.ascontiguousarray(abcd, dtype=abi.QUAD32_DT)
         m, Cc, D = len(gid), int(capacity), int(max_rounds)
-        dcap = m + (len(expired[0]) if expired is not None else 0) if deferred_capacity is None else int(deferred_capacity)
+        dcap = m + (len(expired[0]) if expired is not None else 0) + self.carry if deferred_capacity is None else int(deferred_capacity)
         cnt = np.array([m if count is None else count], np.uint32)
         a = abi.CArrivals()
         a.count, a.capacity, a.gid, a.head, a.abcd = cnt.ctypes.data, m, gid.ctypes.data, head.ctypes.data, abcd.ctypes.data
@@ -594,8 +616,12 @@ class Assembler:
         b.head, b.abcd, b.origin, b.deferred, b.deferred_capacity, b.stats = tick.io.head, tick.io.abcd, origin, deferred, deferred_capacity, stats
         return b
 
-    def route_device(self, decided, routed):
-        """one RG_MEM_DEVICE run of rg_route32 on the table's stream: the assembler's last run, from two structs whose pointers are device-visible"""
+    def route_device(self, decided, routed, carried=None):
+        """one RG_MEM_DEVICE run of rg_route32 on the table's stream: the assembler's last run, from two structs whose pointers are device-visible. carried: an
+        abi.CRoutedCarry over device-visible columns — rg_route32_carry"""
+        if carried is not None:
+            self.table._check(lib().rg_route32_carry(self._h, C.byref(decided), C.byref(routed), C.byref(carried), abi.MEM_DEVICE))
+            return
         self.table._check(lib().rg_route32(self._h, C.byref(decided), C.byref(routed), abi.MEM_DEVICE))
 
     def decided_for_tick(self, tick, origin):
@@ -607,10 +633,11 @@ class Assembler:
         return d
 
     def route(self, gid, count, rounds, origin, row, persist32, capacity, max_rounds, arrival_capacity, expired_capacity=None, send=None,
-              persist_capacity=None, attention_capacity=None, send_capacity=None, fill=0xAB):
+              persist_capacity=None, attention_capacity=None, send_capacity=None, fill=0xAB, carried=False):
         """one synchronous RG_MEM_HOST run of rg_route32 on numpy arrays (gid [C]; origin / row / persist32 [D * C]; send [(P - 1) * C] or None) ->
         SimpleNamespace(cell, row, persist32 [arrival_capacity], expired_cell / _row / _persist32 [expired_capacity] (None: no expired columns), persist_list,
-        attention, send_list, send_offset [P], counts [4]); every output held `fill` bytes before the run. A list capacity of None holds every possible item."""
+        attention, send_list, send_offset [P], counts [4]); every output held `fill` bytes before the run. A list capacity of None holds every possible item.
+        carried=True: rg_route32_carry, and carried_cell / _row / _persist32 [the carry's capacity] with them."""
         import types
         Cc, D, F = int(capacity), int(max_rounds), self.table.cluster - 1
         col = lambda a, dt: np.ascontiguousarray(a, dtype=dt)      # noqa: E731
@@ -641,6 +668,12 @@ class Assembler:
                                                                                       out.expired_persist32.ctypes.data)
         r.persist_list, r.persist_capacity, r.attention, r.attention_capacity = (out.persist_list.ctypes.data if pcap else None), pcap, (out.attention.ctypes.data if acap else None), acap
         r.send_list, r.send_capacity, r.send_offset, r.counts = (out.send_list.ctypes.data if scap else None), scap, out.send_offset.ctypes.data, out.counts.ctypes.data
+        if carried:
+            out.carried_cell, out.carried_row, out.carried_persist32 = blank(np.uint32, self.carry), blank(abi.OUT32_DT, self.carry), blank(abi.PERSIST32_DT, self.carry)
+            rc = abi.CRoutedCarry()
+            rc.capacity, rc.cell, rc.row, rc.persist32 = self.carry, out.carried_cell.ctypes.data, out.carried_row.ctypes.data, out.carried_persist32.ctypes.data
+            self.table._check(lib().rg_route32_carry(self._h, C.byref(d), C.byref(r), C.byref(rc), abi.MEM_HOST))
+            return out
         self.table._check(lib().rg_route32(self._h, C.byref(d), C.byref(r), abi.MEM_HOST))
         return out
 
