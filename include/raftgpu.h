@@ -921,6 +921,72 @@ int rg_assembler_carry_read(rg_assembler_t *a, int which, uint32_t capacity, uin
 typedef struct { uint32_t capacity; uint32_t *cell; rg_out32_t *row; rg_persist32_t *persist32; } rg_routed_carry_t;   /* [capacity] each */
 int rg_route32_carry(rg_assembler_t *a, const rg_decided_t *in, const rg_routed_t *out, const rg_routed_carry_t *carried, int memspace);
 
+/* ---- WHICH GROUPS NEED THE HOST, AND STATE BY A LIST OF GROUPS (new symbols only; the ABI stays 6) ---------------------------------------------------
+ * A host with 65 536 to a million groups asks the table two things that rg_read_state over the whole table — some 200 bytes a group at five nodes, through
+ * 5 + K + 2(P-1) copies — answers far too dearly: WHICH groups are in a given condition, and the state of EXACTLY these groups, out or in. Both are plain device
+ * work and touch no decision.
+ *
+ * rg_scan: ONE STREAMING PASS OVER THE TABLE. Every group gets a CLASS WORD, the bits below, from its state, its timer ticket, its index base and the three
+ * thresholds of the query. A group is SELECTED iff (any == 0 || (word & any) != 0) && (word & all) == all && (word & none) == 0.
+ *   - bits (optional, [groups]): the class word of EVERY group.
+ *   - list: the gids of the first min(selected, list_capacity) selected groups, ASCENDING. Entries beyond that are NOT TOUCHED; NULL with a capacity of 0 is legal.
+ *   - summary[RG_SCAN_SUMMARY] (required): [b], b < 16, the number of groups with bit b set; [16] the number of selected groups — the true count, which may exceed
+ *     list_capacity; [17] the largest current_term; [18] the largest and [19] the sum of last_index - commit_index over the groups with a log, a negative
+ *     difference counting as 0; [20] the largest last_index - match_index[j] over the followers of prepared leaders with a log, likewise; [21 .. 23] are 0.
+ * Every output is a function of the table and the query alone, bit for bit, run after run: the list is compacted by ballot, popcount and prefix sum, nothing is
+ * appended through an atomic, and no kernel waits for another workgroup. It works for every cluster size a table takes, with no option.
+ *
+ * RG_SCAN_OFF_IMAGE says that a compact-row launch (rg_submit32, rg_submit32c*, the ticks) cannot START this group's workgroup on the 32-bit body: the 64 groups
+ * it shares a workgroup with are then decided in 64 bits, which rg_wide_body_workgroups counts and this bit locates. It is the state's half of that check — a term
+ * or an index (relative to the group's index base: "the index base of the compact formats") outside [0, 2^30), a role epoch, vote count or node slot outside its
+ * domain, an epoch.index at or below a non-zero base, a negative base, a follower record of a prepared group without an image — on the words the step kernel
+ * itself loads: for a group whose log is EMPTY that includes the window and run slot 0 the log's last flush left behind in the table, which rg_read_state reports
+ * as zeros. The peer columns of an UNPREPARED group are not looked at, whatever they hold, as the step kernel does not stage them. What belongs to a launch — a
+ * table built with RG_FORCE_WIDE=1, a row outside the format's domain, a value that leaves the image while the launch runs — is not the state's and is not here.
+ *
+ * MEMSPACES, as the route's. RG_MEM_DEVICE: bits, list and summary are device-visible (rg_dev_alloc / rg_host_alloc); the call is asynchronous on the table's
+ * stream, synchronises nothing and decides nothing on the host from device data — its grids are sized from the group count, so a scan queues right behind
+ * rg_tick2_launch. Its scratch, 12 bytes per wavefront of groups and 192 per workgroup, is the table's: allocated by the first scan, freed with the table.
+ * RG_MEM_HOST: host arrays, staged out, synchronous; of the list only what was written is copied back.
+ * Refused (-1, with a message, before any launch): a NULL query, result or summary; a NULL list with a capacity other than 0; reserved != 0; a mask bit above 15;
+ * backlog or lag outside [0, 2^62]; an unknown memspace and, in RG_MEM_DEVICE, a pointer that is neither device memory nor page-locked host memory. */
+#define RG_SCAN_FOLLOWER         (1u << 0)
+#define RG_SCAN_CANDIDATE        (1u << 1)
+#define RG_SCAN_LEADER           (1u << 2)
+#define RG_SCAN_NO_LEADER        (1u << 3)   /* Follower and current_leader == RG_NO_NODE */
+#define RG_SCAN_TIMEOUT_DETECTED (1u << 4)
+#define RG_SCAN_EMPTY_LOG        (1u << 5)   /* run_count == 0 */
+#define RG_SCAN_RUNS_FULL        (1u << 6)   /* run_count == RG_TERM_RUNS: the next run pushes the oldest out, a lookup into it answers RG_NEED_HOST */
+#define RG_SCAN_BACKLOG          (1u << 7)   /* log not empty and last_index - commit_index > backlog */
+#define RG_SCAN_UNPREPARED       (1u << 8)   /* Leader and !repl_prepared */
+#define RG_SCAN_PENDING_INSTALL  (1u << 9)   /* prepared Leader, some follower's pendingInstallation set */
+#define RG_SCAN_LAGGING          (1u << 10)  /* prepared Leader, log not empty, some follower j: last_index - match_index[j] > lag */
+#define RG_SCAN_OFF_IMAGE        (1u << 11)  /* the group's state cannot START a compact launch on the 32-bit body (above) */
+#define RG_SCAN_HAS_BASE         (1u << 12)  /* index base != 0 */
+#define RG_SCAN_NO_TICKET        (1u << 13)  /* timer deadline == 0 */
+#define RG_SCAN_TICKET_FIRED     (1u << 14)  /* timer deadline == -1 */
+#define RG_SCAN_OVERDUE          (1u << 15)  /* deadline > 0 and deadline <= now */
+#define RG_SCAN_SUMMARY 24
+typedef struct { uint32_t any, all, none; uint32_t reserved; int64_t backlog, lag, now; } rg_scan_query_t;
+typedef struct {
+    uint32_t *bits;                              /* optional [groups]: the class word of every group */
+    uint32_t *list; uint32_t list_capacity;      /* gids of the selected groups, ASCENDING; NULL with capacity 0 is legal */
+    uint64_t *summary;                           /* [RG_SCAN_SUMMARY], required */
+} rg_scan_result_t;
+int rg_scan(rg_table_t *t, const rg_scan_query_t *q, const rg_scan_result_t *out, int memspace);
+
+/* STATE BY LIST: rg_read_state / rg_load_state for the n groups gid[0 .. n), host arrays, synchronous. Element i of every column is group gid[i], in exactly the
+ * layout the range calls have for count = n: run_offset[i] = i * RG_TERM_RUNS on read, the peers of element i at i * (P - 1) + j. A gather (scatter) kernel packs
+ * the listed groups' columns into (out of) one contiguous image in device memory — the table's, grown on demand, freed with the table; running out answers -2 — so
+ * the number of copies does not depend on n or on how the gids are scattered: two per call. n = 0 returns 0; n above the group count is refused.
+ * READ takes the gids in any order, repeats included; a gid at or above the group count is refused, the message names its index, and nothing is written.
+ * LOAD wants DISTINCT gids — a repeat is refused and named — and validates every row as rg_load_state does, the group number in the message being the gid, BEFORE
+ * anything reaches the device: a refused call changes nothing. The listed groups get exactly what rg_load_state gives them — the state, no timer ticket, the
+ * timers' role epoch, zeroed health statistics and, with RG_OPT_DEVICE_IN_FLIGHT, nothing in flight — and every other group of every column stays bit for bit
+ * what it was. */
+int rg_read_state_list(rg_table_t *t, uint32_t n, const uint32_t *gid, rg_group_state_t *dst);
+int rg_load_state_list(rg_table_t *t, uint32_t n, const uint32_t *gid, const rg_group_state_t *src);
+
 /* ---- device memory helpers (so a host without its own HIP binding can keep batches in HBM) --- */
 /* Page-locked host memory for RG_MEM_HOST batches (JNI: wrap it with NewDirectByteBuffer): staging then runs at PCIe
  * speed instead of through the driver's pageable bounce buffers. */
@@ -949,7 +1015,8 @@ int rg_timing_end(rg_table_t *t, double *elapsed_ms);
 int rg_counters_read(rg_table_t *t, uint64_t counters[RG_NUM_COUNTERS], int reset);
 /* Workgroups (64 groups each) of compact-row launches (rg_submit32 / rg_submit32c / rg_submit_async_packed) that were decided by the 64-bit body since the
  * last reset: a value of theirs left the 32-bit image (include/raftgpu.h, rg_submit32; with index bases: "the index base of the compact formats"). Results
- * are the same either way; the count tells a host that groups have outgrown their bases. Waits for the stream. */
+ * are the same either way; the count tells a host that groups have outgrown their bases. Waits for the stream.
+ * WHICH groups: rg_scan with RG_SCAN_OFF_IMAGE in `any` lists them. */
 int rg_wide_body_workgroups(rg_table_t *t, uint64_t *count, int reset);
 /* Plain streaming-copy kernel over `bytes` of scratch on this device: returns achieved GB/s
  * (read+write) — the measured-copy roofline reported next to the 8 TB/s spec. */

@@ -169,6 +169,22 @@ ROUTE_CARRIED, ROUTE_SPILLED = 0x80000000, 0xFFFFFFFE     # rg_route32_carry: a 
 CARRY_NEXT, CARRY_LAST = 0, 1                             # rg_assembler_carry_read: the carry the next run will read / the one the last run read
 EXPIRED_UNTRUSTED = 0xFFFFFFFF                            # *expired_count of a tick whose look-back ran into its bound
 
+# rg_scan: the bits of a group's class word (include/raftgpu.h), in bit order; the words of its summary
+SCAN_BIT_NAMES = ("FOLLOWER", "CANDIDATE", "LEADER", "NO_LEADER", "TIMEOUT_DETECTED", "EMPTY_LOG", "RUNS_FULL", "BACKLOG", "UNPREPARED", "PENDING_INSTALL", "LAGGING",
+                  "OFF_IMAGE", "HAS_BASE", "NO_TICKET", "TICKET_FIRED", "OVERDUE")
+(SCAN_FOLLOWER, SCAN_CANDIDATE, SCAN_LEADER, SCAN_NO_LEADER, SCAN_TIMEOUT_DETECTED, SCAN_EMPTY_LOG, SCAN_RUNS_FULL, SCAN_BACKLOG, SCAN_UNPREPARED,
+ SCAN_PENDING_INSTALL, SCAN_LAGGING, SCAN_OFF_IMAGE, SCAN_HAS_BASE, SCAN_NO_TICKET, SCAN_TICKET_FIRED, SCAN_OVERDUE) = (1 << b for b in range(16))
+SCAN_SUMMARY = 24
+SCAN_SELECTED, SCAN_MAX_TERM, SCAN_MAX_BACKLOG, SCAN_SUM_BACKLOG, SCAN_MAX_LAG = 16, 17, 18, 19, 20      # summary[b < 16]: groups with bit b set
+
+
+class CScanQuery(C.Structure):         # rg_scan_query_t
+    _fields_ = [("any", C.c_uint32), ("all", C.c_uint32), ("none", C.c_uint32), ("reserved", C.c_uint32), ("backlog", C.c_int64), ("lag", C.c_int64), ("now", C.c_int64)]
+
+
+class CScanResult(C.Structure):        # rg_scan_result_t
+    _fields_ = [("bits", C.c_void_p), ("list", C.c_void_p), ("list_capacity", C.c_uint32), ("summary", C.c_void_p)]
+
 
 _STATE_FIELDS = [
     ("current_term", np.int64, 1),

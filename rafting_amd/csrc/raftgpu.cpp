@@ -19,6 +19,7 @@
 #include "rg_device.hpp"
 #include "rg_assemble.hpp"
 #include "rg_route.hpp"
+#include "rg_scan.hpp"
 
 using rg::DevTable;
 using rg::I64x2;
@@ -38,6 +39,9 @@ struct BatchCols {
 
 // the table's buffers of the small entry points: rg_replicate (heartbeat, in-flight, send heads, send rows), rg_timers_expired, rg_health_failure, rg_ready
 enum Aux { X_HB, X_FL, X_SH, X_SS, X_TGID, X_HGID, X_HSLOT, X_HFLAG, X_HDONE, X_READY, X_COLUMNS };
+// ... of rg_scan (its scratch: per-wavefront counts and ballots, per-workgroup partial summaries; RG_MEM_HOST: the three outputs) and of the state lists (the
+// gids and the image of their columns)
+enum Scan { S_WC, S_SEL, S_PART, S_BITS, S_LIST, S_SUMMARY, L_GID, L_IMAGE, S_COLUMNS };
 
 struct PipeSlot {                               // one batch in flight on the pipelined host-memory path (rg_submit_async)
     BatchCols c;
@@ -63,6 +67,7 @@ struct rg_table {
     uint32_t simds = 1024;                      // SIMDs of the device (CUs x 4)
     BatchCols st;                               // the serial RG_MEM_HOST path: one batch at a time, shared by every entry point that stages one of its columns
     Staging aux[X_COLUMNS];
+    Staging scan[S_COLUMNS];
     bool timing = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
     size_t ev_used = 0;
@@ -374,6 +379,7 @@ int rg_table_destroy(rg_table_t *t)
     for (void *c : cols) if (c) (void)hipFree(c);
     release(t->st.col, C_COLUMNS);
     release(t->aux, X_COLUMNS);
+    release(t->scan, S_COLUMNS);
     for (PipeSlot &sl : t->pipe) {
         if (sl.down) (void)hipEventSynchronize(sl.down);
         release(sl.c.col, C_COLUMNS);
@@ -487,114 +493,79 @@ static int step_lanes(const rg_table *t, uint32_t count)
     return wavefronts <= t->simds ? 0 : 64;
 }
 
-static bool state_complete(const rg_group_state_t *s)
-{
-    return s->current_term && s->voted_for && s->role && s->current_leader && s->timeout_detected && s->repl_prepared &&
-           s->role_epoch && s->votes && s->elected_epoch && s->elected_term && s->commit_index && s->epoch_index &&
-           s->epoch_term && s->first_index && s->last_index && s->run_count && s->run_offset && s->run_start && s->run_term &&
-           s->peer_last_epoch && s->peer_next_index && s->peer_match_index && s->peer_rejection && s->peer_pending;
-}
+extern "C++" {
+// The image of n groups as rg_load_state / rg_read_state move it: (5 + K + 2F) columns of n 16-byte elements, in this order. The range calls copy column by column
+// between it and the table; the list calls (rg_read_state_list / rg_load_state_list) move it whole, to and from the one a gather / scatter kernel packs (rg_scan.hpp).
+struct StateImage {
+    std::vector<I64x2> cells;                       // one allocation: column c at c * n
+    I64x2 *tc, *ep, *win, *runs, *en;
+    rg::Ident *id;
+    rg::Elect *el;
+    rg::Match *pm;
+    StateImage(size_t n, size_t F) : cells((5 + rg::K + 2 * F) * (n ? n : 1))
+    {
+        static_assert(sizeof(rg::Ident) == 16 && sizeof(rg::Elect) == 16 && sizeof(rg::Match) == 16, "16-byte columns");
+        I64x2 *b = cells.data();
+        tc = b; ep = b + n; win = b + 2 * n; id = reinterpret_cast<rg::Ident *>(b + 3 * n); el = reinterpret_cast<rg::Elect *>(b + 4 * n);
+        runs = b + 5 * n; en = runs + (size_t)rg::K * n; pm = reinterpret_cast<rg::Match *>(en + F * n);
+    }
+    size_t bytes() const { return cells.size() * sizeof(I64x2); }
+};
 
-int rg_load_state(rg_table_t *t, uint32_t first, uint32_t count, const rg_group_state_t *s)
+// rows 0 .. n - 1 of `s`, validated, into the image; row i is group first + i, or gid[i] (the number the messages name)
+static int pack_state(rg_table *t, const char *who, const rg_group_state_t *s, size_t n, uint32_t first, const uint32_t *gid, StateImage &im)
 {
-    if (!t) return -1;
-    if (!s || !state_complete(s)) return fail(t, -1, "rg_load_state: src or one of its columns is NULL");
-    if ((uint64_t)first + count > t->G) return fail(t, -1, "rg_load_state: range [%u, %u) exceeds %u groups", first, first + count, t->G);
-    if (count == 0) return 0;
-    if (bind(t)) return -2;
-    const size_t n = count, F = t->F, G = t->G;
-    std::vector<I64x2> tc(n), ep(n), win(n), runs(n * rg::K), en(n * F);
-    std::vector<rg::Ident> id(n);
-    std::vector<rg::Elect> el(n);
-    std::vector<rg::Match> pm(n * F);
+    const size_t F = t->F;
+    auto group = [&](size_t i) { return gid ? (size_t)gid[i] : first + i; };
     for (size_t i = 0; i < n; i++) {
         const int32_t role = s->role[i];
-        if (role < RG_FOLLOWER || role > RG_LEADER) return fail(t, -1, "rg_load_state: group %zu role %d", first + i, role);
+        if (role < RG_FOLLOWER || role > RG_LEADER) return fail(t, -1, "%s: group %zu role %d", who, group(i), role);
         if (s->voted_for[i] < RG_NO_NODE || s->voted_for[i] >= (int32_t)t->P || s->current_leader[i] < RG_NO_NODE ||
             s->current_leader[i] >= (int32_t)t->P)
-            return fail(t, -1, "rg_load_state: group %zu node slot out of range", first + i);
+            return fail(t, -1, "%s: group %zu node slot out of range", who, group(i));
         const uint32_t total = s->run_count[i], off = s->run_offset[i];
         const uint32_t rc = total > (uint32_t)rg::K ? (uint32_t)rg::K : total;
         int64_t fi = 0, la = 0;
         if (total) {
             fi = s->first_index[i]; la = s->last_index[i];
             if (s->run_start[off] != fi || la < s->run_start[off + total - 1])
-                return fail(t, -1, "rg_load_state: group %zu runs do not span [first,last]", first + i);
+                return fail(t, -1, "%s: group %zu runs do not span [first,last]", who, group(i));
             if (fi != s->epoch_index[i] && fi != s->epoch_index[i] + 1)
-                return fail(t, -1, "rg_load_state: group %zu first index %lld is neither epoch.index nor epoch.index+1",
-                            first + i, (long long)fi);
+                return fail(t, -1, "%s: group %zu first index %lld is neither epoch.index nor epoch.index+1",
+                            who, group(i), (long long)fi);
             for (uint32_t k = 1; k < total; k++)
                 if (s->run_start[off + k] <= s->run_start[off + k - 1] || s->run_term[off + k] == s->run_term[off + k - 1])
-                    return fail(t, -1, "rg_load_state: group %zu runs are not maximal ascending runs", first + i);
+                    return fail(t, -1, "%s: group %zu runs are not maximal ascending runs", who, group(i));
         }
-        tc[i] = I64x2{s->current_term[i], s->commit_index[i]};
-        ep[i] = I64x2{s->epoch_index[i], s->epoch_term[i]};
-        win[i] = I64x2{fi, la};
+        im.tc[i] = I64x2{s->current_term[i], s->commit_index[i]};
+        im.ep[i] = I64x2{s->epoch_index[i], s->epoch_term[i]};
+        im.win[i] = I64x2{fi, la};
         uint32_t pend = 0;
         for (size_t j = 0; j < F; j++) {
-            en[j * n + i] = I64x2{s->peer_last_epoch[i * F + j], s->peer_next_index[i * F + j]};
-            pm[j * n + i] = rg::Match{s->peer_match_index[i * F + j], s->peer_rejection[i * F + j], 0};
+            im.en[j * n + i] = I64x2{s->peer_last_epoch[i * F + j], s->peer_next_index[i * F + j]};
+            im.pm[j * n + i] = rg::Match{s->peer_match_index[i * F + j], s->peer_rejection[i * F + j], 0};
             if (s->peer_pending[i * F + j]) pend |= 1u << j;
         }
         for (uint32_t k = 0; k < (uint32_t)rg::K; k++) {
             const bool have = k < rc;
-            runs[(size_t)k * n + i] = have ? I64x2{s->run_start[off + total - rc + k], s->run_term[off + total - rc + k]} : I64x2{0, 0};
+            im.runs[(size_t)k * n + i] = have ? I64x2{s->run_start[off + total - rc + k], s->run_term[off + total - rc + k]} : I64x2{0, 0};
         }
         const uint32_t meta = (uint32_t)role | (s->timeout_detected[i] ? rg::META_TD : 0u) |
                               (s->repl_prepared[i] ? rg::META_PREP : 0u) | (rc << rg::META_RC_SHIFT) |
                               (pend << rg::META_PEND_SHIFT);
-        id[i] = rg::Ident{s->voted_for[i], s->current_leader[i], s->role_epoch[i], meta};
-        el[i] = rg::Elect{s->elected_term[i], s->elected_epoch[i], s->votes[i]};
+        im.id[i] = rg::Ident{s->voted_for[i], s->current_leader[i], s->role_epoch[i], meta};
+        im.el[i] = rg::Elect{s->elected_term[i], s->elected_epoch[i], s->votes[i]};
     }
-    hipStream_t st = t->stream;
-    HIP_TRY(t, hipMemcpyAsync(t->dt.term_commit + first, tc.data(), n * sizeof(I64x2), hipMemcpyHostToDevice, st));
-    HIP_TRY(t, hipMemcpyAsync(t->dt.epoch + first, ep.data(), n * sizeof(I64x2), hipMemcpyHostToDevice, st));
-    HIP_TRY(t, hipMemcpyAsync(t->dt.window + first, win.data(), n * sizeof(I64x2), hipMemcpyHostToDevice, st));
-    HIP_TRY(t, hipMemcpyAsync(t->dt.ident + first, id.data(), n * sizeof(rg::Ident), hipMemcpyHostToDevice, st));
-    HIP_TRY(t, hipMemcpyAsync(t->dt.elect + first, el.data(), n * sizeof(rg::Elect), hipMemcpyHostToDevice, st));
-    for (size_t k = 0; k < (size_t)rg::K; k++)
-        HIP_TRY(t, hipMemcpyAsync(t->dt.runs + k * G + first, runs.data() + k * n, n * sizeof(I64x2), hipMemcpyHostToDevice, st));
-    for (size_t j = 0; j < F; j++) {
-        HIP_TRY(t, hipMemcpyAsync(t->dt.peer_en + j * G + first, en.data() + j * n, n * sizeof(I64x2), hipMemcpyHostToDevice, st));
-        HIP_TRY(t, hipMemcpyAsync(t->dt.peer_m + j * G + first, pm.data() + j * n, n * sizeof(rg::Match), hipMemcpyHostToDevice, st));
-    }
-    HIP_TRY(t, hipMemsetAsync(t->timer_deadline + first, 0, n * sizeof(int64_t), st));   // loaded groups hold no timer ticket yet
-    HIP_TRY(t, hipMemcpyAsync(t->timer_epoch + first, s->role_epoch, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    for (size_t j = 0; j < F; j++) {                                                       // ... and fresh health statistics
-        HIP_TRY(t, hipMemsetAsync(t->health_ok + j * G + first, 0, n * sizeof(int64_t), st));
-        HIP_TRY(t, hipMemsetAsync(t->health_fail + j * G + first, 0, n * sizeof(int64_t), st));
-        HIP_TRY(t, hipMemsetAsync(t->health_recent + j * G + first, 0, n * sizeof(int32_t), st));
-        if (t->in_flight) HIP_TRY(t, hipMemsetAsync(t->in_flight + j * G + first, 0, n * sizeof(uint16_t), st));   // ... with nothing in flight
-    }
-    HIP_TRY(t, hipStreamSynchronize(st));
     return 0;
 }
 
-int rg_read_state(rg_table_t *t, uint32_t first, uint32_t count, rg_group_state_t *d)
+// ... and back: the image into rows 0 .. n - 1 of `d`
+static void unpack_state(const StateImage &im, size_t n, size_t F, rg_group_state_t *d)
 {
-    if (!t) return -1;
-    if (!d || !state_complete(d)) return fail(t, -1, "rg_read_state: dst or one of its columns is NULL");
-    if ((uint64_t)first + count > t->G) return fail(t, -1, "rg_read_state: range exceeds %u groups", t->G);
-    if (count == 0) return 0;
-    if (bind(t)) return -2;
-    const size_t n = count, F = t->F, G = t->G;
-    std::vector<I64x2> tc(n), ep(n), win(n), runs(n * rg::K), en(n * F);
-    std::vector<rg::Ident> id(n);
-    std::vector<rg::Elect> el(n);
-    std::vector<rg::Match> pm(n * F);
-    hipStream_t st = t->stream;
-    HIP_TRY(t, hipMemcpyAsync(tc.data(), t->dt.term_commit + first, n * sizeof(I64x2), hipMemcpyDeviceToHost, st));
-    HIP_TRY(t, hipMemcpyAsync(ep.data(), t->dt.epoch + first, n * sizeof(I64x2), hipMemcpyDeviceToHost, st));
-    HIP_TRY(t, hipMemcpyAsync(win.data(), t->dt.window + first, n * sizeof(I64x2), hipMemcpyDeviceToHost, st));
-    HIP_TRY(t, hipMemcpyAsync(id.data(), t->dt.ident + first, n * sizeof(rg::Ident), hipMemcpyDeviceToHost, st));
-    HIP_TRY(t, hipMemcpyAsync(el.data(), t->dt.elect + first, n * sizeof(rg::Elect), hipMemcpyDeviceToHost, st));
-    for (size_t k = 0; k < (size_t)rg::K; k++)
-        HIP_TRY(t, hipMemcpyAsync(runs.data() + k * n, t->dt.runs + k * G + first, n * sizeof(I64x2), hipMemcpyDeviceToHost, st));
-    for (size_t j = 0; j < F; j++) {
-        HIP_TRY(t, hipMemcpyAsync(en.data() + j * n, t->dt.peer_en + j * G + first, n * sizeof(I64x2), hipMemcpyDeviceToHost, st));
-        HIP_TRY(t, hipMemcpyAsync(pm.data() + j * n, t->dt.peer_m + j * G + first, n * sizeof(rg::Match), hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(t, hipStreamSynchronize(st));
+    const I64x2 *tc = im.tc, *ep = im.ep, *win = im.win, *runs = im.runs, *en = im.en;
+    const rg::Ident *id = im.id;
+    const rg::Elect *el = im.el;
+    const rg::Match *pm = im.pm;
     for (size_t i = 0; i < n; i++) {
         const uint32_t meta = id[i].meta;
         const uint32_t rc = (meta >> rg::META_RC_SHIFT) & 7u;
@@ -621,6 +592,83 @@ int rg_read_state(rg_table_t *t, uint32_t first, uint32_t count, rg_group_state_
             d->peer_pending[i * F + j] = (pend >> j) & 1u;
         }
     }
+}
+
+}
+
+static bool state_complete(const rg_group_state_t *s)
+{
+    return s->current_term && s->voted_for && s->role && s->current_leader && s->timeout_detected && s->repl_prepared &&
+           s->role_epoch && s->votes && s->elected_epoch && s->elected_term && s->commit_index && s->epoch_index &&
+           s->epoch_term && s->first_index && s->last_index && s->run_count && s->run_offset && s->run_start && s->run_term &&
+           s->peer_last_epoch && s->peer_next_index && s->peer_match_index && s->peer_rejection && s->peer_pending;
+}
+
+int rg_load_state(rg_table_t *t, uint32_t first, uint32_t count, const rg_group_state_t *s)
+{
+    if (!t) return -1;
+    if (!s || !state_complete(s)) return fail(t, -1, "rg_load_state: src or one of its columns is NULL");
+    if ((uint64_t)first + count > t->G) return fail(t, -1, "rg_load_state: range [%u, %u) exceeds %u groups", first, first + count, t->G);
+    if (count == 0) return 0;
+    if (bind(t)) return -2;
+    const size_t n = count, F = t->F, G = t->G;
+    StateImage im(n, F);
+    if (int rc = pack_state(t, "rg_load_state", s, n, first, nullptr, im)) return rc;
+    I64x2 *tc = im.tc, *ep = im.ep, *win = im.win, *runs = im.runs, *en = im.en;
+    rg::Ident *id = im.id;
+    rg::Elect *el = im.el;
+    rg::Match *pm = im.pm;
+    hipStream_t st = t->stream;
+    HIP_TRY(t, hipMemcpyAsync(t->dt.term_commit + first, tc, n * sizeof(I64x2), hipMemcpyHostToDevice, st));
+    HIP_TRY(t, hipMemcpyAsync(t->dt.epoch + first, ep, n * sizeof(I64x2), hipMemcpyHostToDevice, st));
+    HIP_TRY(t, hipMemcpyAsync(t->dt.window + first, win, n * sizeof(I64x2), hipMemcpyHostToDevice, st));
+    HIP_TRY(t, hipMemcpyAsync(t->dt.ident + first, id, n * sizeof(rg::Ident), hipMemcpyHostToDevice, st));
+    HIP_TRY(t, hipMemcpyAsync(t->dt.elect + first, el, n * sizeof(rg::Elect), hipMemcpyHostToDevice, st));
+    for (size_t k = 0; k < (size_t)rg::K; k++)
+        HIP_TRY(t, hipMemcpyAsync(t->dt.runs + k * G + first, runs + k * n, n * sizeof(I64x2), hipMemcpyHostToDevice, st));
+    for (size_t j = 0; j < F; j++) {
+        HIP_TRY(t, hipMemcpyAsync(t->dt.peer_en + j * G + first, en + j * n, n * sizeof(I64x2), hipMemcpyHostToDevice, st));
+        HIP_TRY(t, hipMemcpyAsync(t->dt.peer_m + j * G + first, pm + j * n, n * sizeof(rg::Match), hipMemcpyHostToDevice, st));
+    }
+    HIP_TRY(t, hipMemsetAsync(t->timer_deadline + first, 0, n * sizeof(int64_t), st));   // loaded groups hold no timer ticket yet
+    HIP_TRY(t, hipMemcpyAsync(t->timer_epoch + first, s->role_epoch, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    for (size_t j = 0; j < F; j++) {                                                       // ... and fresh health statistics
+        HIP_TRY(t, hipMemsetAsync(t->health_ok + j * G + first, 0, n * sizeof(int64_t), st));
+        HIP_TRY(t, hipMemsetAsync(t->health_fail + j * G + first, 0, n * sizeof(int64_t), st));
+        HIP_TRY(t, hipMemsetAsync(t->health_recent + j * G + first, 0, n * sizeof(int32_t), st));
+        if (t->in_flight) HIP_TRY(t, hipMemsetAsync(t->in_flight + j * G + first, 0, n * sizeof(uint16_t), st));   // ... with nothing in flight
+    }
+    HIP_TRY(t, hipStreamSynchronize(st));
+    return 0;
+}
+
+int rg_read_state(rg_table_t *t, uint32_t first, uint32_t count, rg_group_state_t *d)
+{
+    if (!t) return -1;
+    if (!d || !state_complete(d)) return fail(t, -1, "rg_read_state: dst or one of its columns is NULL");
+    if ((uint64_t)first + count > t->G) return fail(t, -1, "rg_read_state: range exceeds %u groups", t->G);
+    if (count == 0) return 0;
+    if (bind(t)) return -2;
+    const size_t n = count, F = t->F, G = t->G;
+    StateImage im(n, F);
+    I64x2 *tc = im.tc, *ep = im.ep, *win = im.win, *runs = im.runs, *en = im.en;
+    rg::Ident *id = im.id;
+    rg::Elect *el = im.el;
+    rg::Match *pm = im.pm;
+    hipStream_t st = t->stream;
+    HIP_TRY(t, hipMemcpyAsync(tc, t->dt.term_commit + first, n * sizeof(I64x2), hipMemcpyDeviceToHost, st));
+    HIP_TRY(t, hipMemcpyAsync(ep, t->dt.epoch + first, n * sizeof(I64x2), hipMemcpyDeviceToHost, st));
+    HIP_TRY(t, hipMemcpyAsync(win, t->dt.window + first, n * sizeof(I64x2), hipMemcpyDeviceToHost, st));
+    HIP_TRY(t, hipMemcpyAsync(id, t->dt.ident + first, n * sizeof(rg::Ident), hipMemcpyDeviceToHost, st));
+    HIP_TRY(t, hipMemcpyAsync(el, t->dt.elect + first, n * sizeof(rg::Elect), hipMemcpyDeviceToHost, st));
+    for (size_t k = 0; k < (size_t)rg::K; k++)
+        HIP_TRY(t, hipMemcpyAsync(runs + k * n, t->dt.runs + k * G + first, n * sizeof(I64x2), hipMemcpyDeviceToHost, st));
+    for (size_t j = 0; j < F; j++) {
+        HIP_TRY(t, hipMemcpyAsync(en + j * n, t->dt.peer_en + j * G + first, n * sizeof(I64x2), hipMemcpyDeviceToHost, st));
+        HIP_TRY(t, hipMemcpyAsync(pm + j * n, t->dt.peer_m + j * G + first, n * sizeof(rg::Match), hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(t, hipStreamSynchronize(st));
+    unpack_state(im, n, F, d);
     return 0;
 }
 
@@ -1500,6 +1548,118 @@ int rg_assembler_carry_read(rg_assembler_t *a, int which, uint32_t capacity, uin
         HIP_TRY(t, hipMemcpyAsync(abcd, c.abcd, k * sizeof(rg_ev_quad32_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(t, hipStreamSynchronize(s));
     }
+    return 0;
+}
+
+/* ---- the table's groups by class, and state by a list of groups (include/raftgpu.h, rg_scan.hpp) --------------------------------------------- */
+
+int rg_scan(rg_table_t *t, const rg_scan_query_t *q, const rg_scan_result_t *out, int memspace)
+{
+    if (!t) return -1;
+    const char *who = "rg_scan";
+    if (!q || !out) return fail(t, -1, "%s: NULL query or result", who);
+    if (!out->summary) return fail(t, -1, "%s: summary is required", who);
+    if (!out->list && out->list_capacity) return fail(t, -1, "%s: a NULL list with a capacity of %u", who, out->list_capacity);
+    if (q->reserved != 0) return fail(t, -1, "%s: reserved is %u, not 0", who, q->reserved);
+    if ((q->any | q->all | q->none) > 0xFFFFu) return fail(t, -1, "%s: a mask names a bit above 15 (any 0x%x, all 0x%x, none 0x%x)", who, q->any, q->all, q->none);
+    const int64_t most = (int64_t)1 << 62;
+    if (q->backlog < 0 || q->backlog > most) return fail(t, -1, "%s: backlog %lld outside [0, 2^62]", who, (long long)q->backlog);
+    if (q->lag < 0 || q->lag > most) return fail(t, -1, "%s: lag %lld outside [0, 2^62]", who, (long long)q->lag);
+    if (memspace != RG_MEM_DEVICE && memspace != RG_MEM_HOST) return fail(t, -1, "%s: unknown memspace %d", who, memspace);
+    const size_t G = t->G, blocks = (G + 255) / 256, waves = blocks * 4;
+    rg::ScanParams p{};
+    p.t = t->dt; p.deadline = t->timer_deadline; p.has_bases = t->has_bases; p.followers = t->F;
+    p.any = q->any; p.all = q->all; p.none = q->none; p.backlog = q->backlog; p.lag = q->lag; p.now = q->now;
+    p.list_cap = out->list_capacity;
+    void *v[3] = {};
+    if (memspace == RG_MEM_DEVICE) {
+        const struct { const void *ptr; const char *what; } cols[] = {{out->bits, "bits"}, {out->list, "list"}, {out->summary, "summary"}};
+        int k = 0;
+        for (const auto &c : cols) if (int rc = device_visible(t, who, c.ptr, c.what, &v[k++])) return rc;
+    }
+    if (bind(t)) return -2;
+    if (stage_out(t, t->scan[S_WC], waves + 1, &p.wc) || stage_out(t, t->scan[S_SEL], waves, &p.sel) || stage_out(t, t->scan[S_PART], blocks * rg::SCAN_WORDS, &p.part)) return -2;
+    hipStream_t s = t->stream;
+    if (memspace == RG_MEM_DEVICE) {
+        p.bits = (uint32_t *)v[0]; p.list = (uint32_t *)v[1]; p.summary = (unsigned long long *)v[2];
+        HIP_TRY(t, rg::launch_scan(p, s));
+        return 0;
+    }
+    if ((out->bits && stage_out(t, t->scan[S_BITS], G, &p.bits)) || (p.list_cap && stage_out(t, t->scan[S_LIST], (size_t)p.list_cap, &p.list)) ||
+        stage_out(t, t->scan[S_SUMMARY], (size_t)RG_SCAN_SUMMARY, &p.summary))
+        return -2;
+    HIP_TRY(t, rg::launch_scan(p, s));
+    uint64_t summary[RG_SCAN_SUMMARY] = {};
+    HIP_TRY(t, col_down(t->scan[S_SUMMARY], summary, 0, (size_t)RG_SCAN_SUMMARY, s));
+    if (out->bits) HIP_TRY(t, col_down(t->scan[S_BITS], out->bits, 0, G, s));
+    HIP_TRY(t, hipStreamSynchronize(s));
+    memcpy(out->summary, summary, sizeof summary);
+    const size_t listed = summary[16] < p.list_cap ? (size_t)summary[16] : p.list_cap;      // entries beyond what was written are not touched
+    if (listed) {
+        HIP_TRY(t, col_down(t->scan[S_LIST], out->list, 0, listed, s));
+        HIP_TRY(t, hipStreamSynchronize(s));
+    }
+    return 0;
+}
+
+// the gids of a state list on the device, and room for the image of their columns
+static int state_list_stage(rg_table *t, uint32_t n, const uint32_t *gid, rg::StateListParams &p)
+{
+    p.t = t->dt; p.n = n; p.followers = t->F;
+    p.deadline = t->timer_deadline; p.timer_epoch = t->timer_epoch; p.ok = t->health_ok; p.fail = t->health_fail; p.recent = t->health_recent; p.in_flight = t->in_flight;
+    if (int rc = stage_in(t, t->scan[L_GID], gid, (size_t)n, t->stream, &p.gid)) return rc;
+    return stage_out(t, t->scan[L_IMAGE], (size_t)rg::state_list_columns(t->F) * n, &p.image);
+}
+
+int rg_read_state_list(rg_table_t *t, uint32_t n, const uint32_t *gid, rg_group_state_t *d)
+{
+    if (!t) return -1;
+    const char *who = "rg_read_state_list";
+    if (n > t->G) return fail(t, -1, "%s: %u groups listed, the table has %u", who, n, t->G);
+    if (n == 0) return 0;
+    if (!gid) return fail(t, -1, "%s: gid is NULL", who);
+    if (!d || !state_complete(d)) return fail(t, -1, "%s: dst or one of its columns is NULL", who);
+    for (uint32_t i = 0; i < n; i++)
+        if (gid[i] >= t->G) return fail(t, -1, "%s: gid[%u] = %u, the table has %u groups", who, i, gid[i], t->G);
+    if (bind(t)) return -2;
+    rg::StateListParams p{};
+    if (int rc = state_list_stage(t, n, gid, p)) return rc;
+    StateImage im(n, t->F);
+    hipStream_t s = t->stream;
+    HIP_TRY(t, rg::launch_state_gather(p, s));
+    HIP_TRY(t, hipMemcpyAsync(im.cells.data(), p.image, im.bytes(), hipMemcpyDeviceToHost, s));
+    HIP_TRY(t, hipStreamSynchronize(s));
+    unpack_state(im, n, t->F, d);
+    return 0;
+}
+
+int rg_load_state_list(rg_table_t *t, uint32_t n, const uint32_t *gid, const rg_group_state_t *src)
+{
+    if (!t) return -1;
+    const char *who = "rg_load_state_list";
+    if (n > t->G) return fail(t, -1, "%s: %u groups listed, the table has %u", who, n, t->G);
+    if (n == 0) return 0;
+    if (!gid) return fail(t, -1, "%s: gid is NULL", who);
+    if (!src || !state_complete(src)) return fail(t, -1, "%s: src or one of its columns is NULL", who);
+    for (uint32_t i = 0; i < n; i++)
+        if (gid[i] >= t->G) return fail(t, -1, "%s: gid[%u] = %u, the table has %u groups", who, i, gid[i], t->G);
+    {   // distinct gids make every destination the store of one lane
+        std::vector<std::pair<uint32_t, uint32_t>> order(n);
+        for (uint32_t i = 0; i < n; i++) order[i] = {gid[i], i};
+        std::sort(order.begin(), order.end());
+        for (uint32_t i = 1; i < n; i++)
+            if (order[i].first == order[i - 1].first)
+                return fail(t, -1, "%s: gid[%u] and gid[%u] both name group %u", who, order[i - 1].second, order[i].second, order[i].first);
+    }
+    StateImage im(n, t->F);
+    if (int rc = pack_state(t, who, src, n, 0, gid, im)) return rc;        // every row, before anything reaches the device
+    if (bind(t)) return -2;
+    rg::StateListParams p{};
+    if (int rc = state_list_stage(t, n, gid, p)) return rc;
+    hipStream_t s = t->stream;
+    HIP_TRY(t, hipMemcpyAsync(p.image, im.cells.data(), im.bytes(), hipMemcpyHostToDevice, s));
+    HIP_TRY(t, rg::launch_state_scatter(p, s));
+    HIP_TRY(t, hipStreamSynchronize(s));
     return 0;
 }
 

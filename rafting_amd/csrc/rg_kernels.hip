@@ -909,7 +909,10 @@ hipError_t launch_tick_tail(const TickTailParams &p, int followers, hipStream_t 
 #ifdef RG_TU_MAIN
 #define RG_ASSEMBLE_KERNELS 1
 #define RG_ROUTE_KERNELS 1
+#define RG_SCAN_KERNELS 1
 #endif
 #include "rg_assemble.hpp"
 // ---- ... and their results back in arrival order (rg_route32)
 #include "rg_route.hpp"
+// ---- the table's groups by class (rg_scan) and a group's columns by a list of gids (rg_read_state_list / rg_load_state_list): load_group and the entry check of narrow_body above
+#include "rg_scan.hpp"

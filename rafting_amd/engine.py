@@ -31,7 +31,7 @@ def exported_symbols():
     """Every entry point include/raftgpu.h declares."""
     return [
         "rg_abi_version", "rg_table_create", "rg_table_destroy", "rg_last_error", "rg_table_groups",
-        "rg_table_cluster", "rg_table_option", "rg_load_state", "rg_read_state", "rg_submit", "rg_submit32", "rg_submit32c", "rg_submit32c_sparse", "rg_submit32c_sparse_rounds", "rg_outcome32_unpack", "rg_outcome32_unpack_rel", "rg_index_base_set", "rg_index_base_get", "rg_index_base_advance", "rg_index_base_advance32", "rg_batch32_pack_rel", "rg_batch32_pack", "rg_submit_async", "rg_submit_async_packed", "rg_submit_wait", "rg_tick_create", "rg_tick_launch", "rg_tick_wait", "rg_tick_destroy", "rg_tick2_create", "rg_tick2_create_sparse", "rg_tick2_create_sparse_rounds", "rg_tick2_launch", "rg_tick2_wait", "rg_tick2_destroy", "rg_assembler_create", "rg_assemble32", "rg_assembler_destroy", "rg_route32", "rg_assembler_carry_enable", "rg_assembler_carry_reset", "rg_assembler_carry_read", "rg_route32_carry", "rg_timers_update32", "rg_health_update32", "rg_sync", "rg_step_kernel", "rg_host_alloc", "rg_host_free", "rg_dev_alloc",
+        "rg_table_cluster", "rg_table_option", "rg_load_state", "rg_read_state", "rg_submit", "rg_submit32", "rg_submit32c", "rg_submit32c_sparse", "rg_submit32c_sparse_rounds", "rg_outcome32_unpack", "rg_outcome32_unpack_rel", "rg_index_base_set", "rg_index_base_get", "rg_index_base_advance", "rg_index_base_advance32", "rg_batch32_pack_rel", "rg_batch32_pack", "rg_submit_async", "rg_submit_async_packed", "rg_submit_wait", "rg_tick_create", "rg_tick_launch", "rg_tick_wait", "rg_tick_destroy", "rg_tick2_create", "rg_tick2_create_sparse", "rg_tick2_create_sparse_rounds", "rg_tick2_launch", "rg_tick2_wait", "rg_tick2_destroy", "rg_assembler_create", "rg_assemble32", "rg_assembler_destroy", "rg_route32", "rg_assembler_carry_enable", "rg_assembler_carry_reset", "rg_assembler_carry_read", "rg_route32_carry", "rg_scan", "rg_read_state_list", "rg_load_state_list", "rg_timers_update32", "rg_health_update32", "rg_sync", "rg_step_kernel", "rg_host_alloc", "rg_host_free", "rg_dev_alloc",
         "rg_dev_free", "rg_copy_to_device", "rg_copy_to_host", "rg_stream", "rg_replicate", "rg_timers_configure", "rg_timers_update",
         "rg_timers_expired", "rg_timers_expired_epochs", "rg_timers_arm", "rg_timers_read", "rg_health_update", "rg_health_failure", "rg_ready", "rg_health_read", "rg_in_flight_read", "rg_in_flight_set",
         "rg_timing_enable",
@@ -139,6 +139,9 @@ def lib():
         L.rg_assembler_carry_reset.argtypes = [vp]
         L.rg_assembler_carry_read.argtypes = [vp, i32, u32, C.POINTER(u32), vp, vp, vp]
         L.rg_route32_carry.argtypes = [vp, C.POINTER(abi.CDecided), C.POINTER(abi.CRouted), C.POINTER(abi.CRoutedCarry), i32]
+        L.rg_scan.argtypes = [vp, C.POINTER(abi.CScanQuery), C.POINTER(abi.CScanResult), i32]
+        L.rg_read_state_list.argtypes = [vp, u32, vp, C.POINTER(abi.CGroupState)]
+        L.rg_load_state_list.argtypes = [vp, u32, vp, C.POINTER(abi.CGroupState)]
         L.rg_timers_update32.argtypes = [vp, u32, vp, vp, vp, i32]
         L.rg_health_update32.argtypes = [vp, u32, vp, vp, vp, i32]
         L.rg_replicate.argtypes = [vp, u32, vp, vp, vp, vp, vp, i32]
@@ -909,6 +912,39 @@ class Table:
         s = st.as_struct()
         self._check(lib().rg_read_state(self._h, first, count, C.byref(s)))
         return st
+
+    def read_state_list(self, gids):
+        """rg_read_state_list -> abi.GroupState whose element i is group gids[i] (any order, repeats allowed)"""
+        g = np.ascontiguousarray(gids, dtype=np.uint32)
+        st = abi.GroupState(len(g), self.cluster)
+        s = st.as_struct()
+        self._check(lib().rg_read_state_list(self._h, len(g), g.ctypes.data, C.byref(s)))
+        return st
+
+    def load_state_list(self, state, gids):
+        """rg_load_state_list: element i of `state` becomes group gids[i] (distinct gids), as load_state would load it"""
+        g = np.ascontiguousarray(gids, dtype=np.uint32)
+        assert len(g) == state.count, (len(g), state.count)
+        s = state.as_struct()
+        self._check(lib().rg_load_state_list(self._h, len(g), g.ctypes.data, C.byref(s)))
+
+    # the table's groups by class -----------------------------------------------------------------
+    def scan(self, any=0, all=0, none=0, backlog=0, lag=0, now=0, capacity=None, bits=True):
+        """one synchronous RG_MEM_HOST rg_scan -> namespace(bits uint32[groups] or None, list uint32[min(selected, capacity)] ascending, summary uint64[abi.SCAN_SUMMARY]);
+        capacity None: room for every group"""
+        import types
+        capacity = self.groups if capacity is None else int(capacity)
+        words = np.zeros(self.groups, np.uint32) if bits else None
+        gids = np.zeros(capacity, np.uint32)
+        summary = np.zeros(abi.SCAN_SUMMARY, np.uint64)
+        q = abi.CScanQuery(any=any, all=all, none=none, reserved=0, backlog=backlog, lag=lag, now=now)
+        r = abi.CScanResult(bits=abi._ptr(words), list=gids.ctypes.data if capacity else None, list_capacity=capacity, summary=summary.ctypes.data)
+        self._check(lib().rg_scan(self._h, C.byref(q), C.byref(r), abi.MEM_HOST))
+        return types.SimpleNamespace(bits=words, list=gids[:min(int(summary[abi.SCAN_SELECTED]), capacity)], summary=summary)
+
+    def scan_device(self, query, result):
+        """one RG_MEM_DEVICE rg_scan on the table's stream: an abi.CScanQuery and an abi.CScanResult whose pointers are device-visible; asynchronous"""
+        self._check(lib().rg_scan(self._h, C.byref(query), C.byref(result), abi.MEM_DEVICE))
 
     # hot path ------------------------------------------------------------------------------------
     def submit(self, batch, out=None, fill=0):
