@@ -987,6 +987,56 @@ int rg_scan(rg_table_t *t, const rg_scan_query_t *q, const rg_scan_result_t *out
 int rg_read_state_list(rg_table_t *t, uint32_t n, const uint32_t *gid, rg_group_state_t *dst);
 int rg_load_state_list(rg_table_t *t, uint32_t n, const uint32_t *gid, const rg_group_state_t *src);
 
+/* ---- WHAT A LAUNCH ASKS THE HOST TO DO, AS LISTS (new symbols only; the ABI stays 6) ---------------------------------------------------------------
+ * rg_submit32c, rg_submit32c_sparse(_rounds) and a rg_tick2_* tick write rg_out32_t row[D][C], and three consumers of a host then each walk all D x C rows to find
+ * the few that carry an instruction for them: the log writer wants the cells with RG_F_LOG_APPEND or RG_F_LOG_TRUNC (RaftLog.truncate / append), the applier
+ * wants one line per group whose commitIndex moved (RaftContext.commitLog -> RaftRoutine.commitState), the repair path wants the RG_NEED_HOST cells. rg_route32
+ * builds such lists only behind an assembler, and neither of the first two. rg_effects32 builds all three from the rows alone, on the device, whatever wrote them.
+ *
+ * THE ROWS. C = capacity is the row stride of a round, D = max_rounds; cell = r * C + i names row i of round r. n = min(*count, C) and R = clamp(*rounds, 1, D) are
+ * read when the run executes, as the tick reads them; a NULL count means n = C, a NULL rounds R = D. Row i belongs to group gid[i], or to group i when gid is NULL
+ * (a dense batch): that is the `gid` of every item below.
+ *
+ * THE RESULT.
+ *   - log_list: {cell, gid} of every cell (r < R, i < n) whose flags carry RG_F_LOG_APPEND or RG_F_LOG_TRUNC, in ascending cell order — round-major, so one group's
+ *     log writes stay in their order. The reader takes log_from and the two flags from row[cell].
+ *   - attention: the same for every cell whose status is RG_NEED_HOST.
+ *   - commit_list: ONE item per row i < n that has at least one round r < R with RG_F_COMMIT, in ascending i. cell is the cell of the LAST such round;
+ *     commit_index and flags are that cell's two words VERBATIM. commit_index is relative to the index base the launch STARTED with, as the rows are: the call does
+ *     not convert it, because the table's base may already have moved (RG_OPT_AUTO_INDEX_BASE). flags lets the reader see RG_F_WIDE_VALUES and go to the overflow
+ *     columns by `cell`.
+ *   - counts[4] = {log items, commit items, attention items, 0}: the true numbers. A count may exceed its list's capacity: the first `capacity` items in the
+ *     stated order are then written. List entries beyond what was written are NOT TOUCHED; a NULL list with a capacity of 0 is legal. Rows >= n and rounds >= R
+ *     are not read.
+ * Every output is a function of the inputs alone, bit for bit, run after run: the lists are compacted by ballot, popcount and prefix sum, nothing is appended
+ * through an atomic, no kernel waits for another workgroup, and every loop is bounded by R or by a span computed on the host.
+ *
+ * MEMSPACES, as the route's. RG_MEM_DEVICE: every pointer of both structs is device-visible (rg_dev_alloc / rg_host_alloc); the call is asynchronous on the
+ * table's stream, synchronises nothing and decides nothing on the host from device data — its grids are sized from C and D and leave early on the n and R they
+ * read. So it queues right behind rg_submit32c*(RG_MEM_DEVICE), or behind rg_tick2_launch with the tick's own count / rounds words, with no host step in between.
+ * Its scratch, three words per wavefront of cells or rows, is the table's: allocated by the first call of a shape, freed with the table. RG_MEM_HOST: host
+ * arrays, staged in (rows 0 .. n - 1 of rounds 0 .. R - 1) and out, synchronous; of the lists only what was written is copied back.
+ * Refused (-1, with a message, before any launch): NULL structs, a NULL row or counts; a NULL list with a capacity other than 0; C = 0 or above the group count;
+ * D = 0 or at or above 2^24 (the rounds of one compact launch, rg_submit32); D x C at or above 2^32; an unknown memspace; in RG_MEM_DEVICE a pointer that is
+ * neither device memory nor page-locked host memory; in RG_MEM_HOST a gid[i], i < n, at or above the group count — the message names it. RG_MEM_DEVICE trusts the
+ * list, as the sparse submit does. Wide rows (rg_outcome_t) are not taken. */
+typedef struct { uint32_t cell; uint32_t gid; int32_t commit_index; uint32_t flags; } rg_commit_item_t;   /* 16 B: commit_list */
+typedef struct {
+    uint32_t          capacity;    /* C: the row stride of a round, 1 .. groups */
+    uint32_t          max_rounds;  /* D */
+    const uint32_t   *gid;         /* [C], or NULL: row i is group i (a dense batch) */
+    const uint32_t   *count;       /* [1], or NULL: n = C */
+    const uint32_t   *rounds;      /* [1], or NULL: R = D */
+    const rg_out32_t *row;         /* [D][C] */
+} rg_effects_in_t;
+typedef struct {
+    rg_route_item_t  *log_list;    uint32_t log_capacity;
+    rg_commit_item_t *commit_list; uint32_t commit_capacity;
+    rg_route_item_t  *attention;   uint32_t attention_capacity;
+    uint32_t         *counts;      /* [4] = {log items, commit items, attention items, 0}, required */
+} rg_effects_t;
+int rg_effects32(rg_table_t *t, const rg_effects_in_t *in, const rg_effects_t *out, int memspace);
+
 /* ---- device memory helpers (so a host without its own HIP binding can keep batches in HBM) --- */
 /* Page-locked host memory for RG_MEM_HOST batches (JNI: wrap it with NewDirectByteBuffer): staging then runs at PCIe
  * speed instead of through the driver's pageable bounce buffers. */

@@ -186,6 +186,19 @@ class CScanResult(C.Structure):        # rg_scan_result_t
     _fields_ = [("bits", C.c_void_p), ("list", C.c_void_p), ("list_capacity", C.c_uint32), ("summary", C.c_void_p)]
 
 
+COMMIT_ITEM_DT = np.dtype([("cell", np.uint32), ("gid", np.uint32), ("commit_index", np.int32), ("flags", np.uint32)])      # rg_commit_item_t: rg_effects32's commit_list
+assert COMMIT_ITEM_DT.itemsize == 16
+
+
+class CEffectsIn(C.Structure):         # rg_effects_in_t
+    _fields_ = [("capacity", C.c_uint32), ("max_rounds", C.c_uint32), ("gid", C.c_void_p), ("count", C.c_void_p), ("rounds", C.c_void_p), ("row", C.c_void_p)]
+
+
+class CEffects(C.Structure):           # rg_effects_t
+    _fields_ = [("log_list", C.c_void_p), ("log_capacity", C.c_uint32), ("commit_list", C.c_void_p), ("commit_capacity", C.c_uint32),
+                ("attention", C.c_void_p), ("attention_capacity", C.c_uint32), ("counts", C.c_void_p)]
+
+
 _STATE_FIELDS = [
     ("current_term", np.int64, 1),
     ("voted_for", np.int32, 1),

@@ -20,6 +20,7 @@
 #include "rg_assemble.hpp"
 #include "rg_route.hpp"
 #include "rg_scan.hpp"
+#include "rg_effects.hpp"
 
 using rg::DevTable;
 using rg::I64x2;
@@ -42,6 +43,8 @@ enum Aux { X_HB, X_FL, X_SH, X_SS, X_TGID, X_HGID, X_HSLOT, X_HFLAG, X_HDONE, X_
 // ... of rg_scan (its scratch: per-wavefront counts and ballots, per-workgroup partial summaries; RG_MEM_HOST: the three outputs) and of the state lists (the
 // gids and the image of their columns)
 enum Scan { S_WC, S_SEL, S_PART, S_BITS, S_LIST, S_SUMMARY, L_GID, L_IMAGE, S_COLUMNS };
+// ... of rg_effects32 (its scratch: the per-wavefront counts of the three lists; RG_MEM_HOST: the words n and R, the batch's gid and row columns, the outputs)
+enum Effects { E_LC, E_AC, E_CC, E_WORDS, E_GID, E_ROW, E_LOG, E_COMMIT, E_ATTENTION, E_COUNTS, E_COLUMNS };
 
 struct PipeSlot {                               // one batch in flight on the pipelined host-memory path (rg_submit_async)
     BatchCols c;
@@ -68,6 +71,7 @@ struct rg_table {
     BatchCols st;                               // the serial RG_MEM_HOST path: one batch at a time, shared by every entry point that stages one of its columns
     Staging aux[X_COLUMNS];
     Staging scan[S_COLUMNS];
+    Staging fx[E_COLUMNS];
     bool timing = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
     size_t ev_used = 0;
@@ -380,6 +384,7 @@ int rg_table_destroy(rg_table_t *t)
     release(t->st.col, C_COLUMNS);
     release(t->aux, X_COLUMNS);
     release(t->scan, S_COLUMNS);
+    release(t->fx, E_COLUMNS);
     for (PipeSlot &sl : t->pipe) {
         if (sl.down) (void)hipEventSynchronize(sl.down);
         release(sl.c.col, C_COLUMNS);
@@ -1659,6 +1664,69 @@ int rg_load_state_list(rg_table_t *t, uint32_t n, const uint32_t *gid, const rg_
     hipStream_t s = t->stream;
     HIP_TRY(t, hipMemcpyAsync(p.image, im.cells.data(), im.bytes(), hipMemcpyHostToDevice, s));
     HIP_TRY(t, rg::launch_state_scatter(p, s));
+    HIP_TRY(t, hipStreamSynchronize(s));
+    return 0;
+}
+
+/* ---- what a launch asks a host to do, as lists (rg_effects32, include/raftgpu.h; kernels: rg_effects.hpp) ------------------------------------ */
+int rg_effects32(rg_table_t *t, const rg_effects_in_t *in, const rg_effects_t *out, int memspace)
+{
+    if (!t) return -1;
+    const char *who = "rg_effects32";
+    if (!in || !out) return fail(t, -1, "%s: NULL rows or lists", who);
+    if (!in->row) return fail(t, -1, "%s: row is required", who);
+    if (!out->counts) return fail(t, -1, "%s: counts is required", who);
+    if (!out->log_list && out->log_capacity) return fail(t, -1, "%s: a NULL log_list with a capacity of %u", who, out->log_capacity);
+    if (!out->commit_list && out->commit_capacity) return fail(t, -1, "%s: a NULL commit_list with a capacity of %u", who, out->commit_capacity);
+    if (!out->attention && out->attention_capacity) return fail(t, -1, "%s: a NULL attention list with a capacity of %u", who, out->attention_capacity);
+    if (in->capacity == 0 || in->capacity > t->G) return fail(t, -1, "%s: capacity %u outside 1 .. %u groups", who, in->capacity, t->G);
+    if (in->max_rounds < 1 || in->max_rounds >= (1u << 24))
+        return fail(t, -1, "%s: max_rounds %u outside 1 .. 2^24 - 1 (the rounds of one compact launch)", who, in->max_rounds);
+    if ((uint64_t)in->capacity * in->max_rounds >= (1ull << 32))
+        return fail(t, -1, "%s: %u x %u cells: a cell index holds fewer than 2^32", who, in->capacity, in->max_rounds);
+    if (memspace != RG_MEM_DEVICE && memspace != RG_MEM_HOST) return fail(t, -1, "%s: unknown memspace %d", who, memspace);
+    const uint32_t C = in->capacity, D = in->max_rounds;
+    const size_t cells = (size_t)C * D;
+    rg::EffectsParams p{};
+    p.C = C; p.D = D; p.log_cap = out->log_capacity; p.commit_cap = out->commit_capacity; p.attention_cap = out->attention_capacity;
+    p.cspan = rg::effects_span(cells); p.rspan = rg::effects_span(C);
+    p.Wc = (uint32_t)((cells + p.cspan - 1) / p.cspan); p.Wr = (C + p.rspan - 1) / p.rspan;
+    if (memspace == RG_MEM_DEVICE) {
+        void *v[8] = {};
+        const struct { const void *ptr; const char *what; } cols[] = {{in->gid, "gid"}, {in->count, "count"}, {in->rounds, "rounds"}, {in->row, "row"},
+            {out->log_list, "log_list"}, {out->commit_list, "commit_list"}, {out->attention, "attention"}, {out->counts, "counts"}};
+        int k = 0;
+        for (const auto &c : cols) if (int rc = device_visible(t, who, c.ptr, c.what, &v[k++])) return rc;
+        if (bind(t)) return -2;
+        if (stage_out(t, t->fx[E_LC], (size_t)p.Wc + 1, &p.lc) || stage_out(t, t->fx[E_AC], (size_t)p.Wc + 1, &p.ac) || stage_out(t, t->fx[E_CC], (size_t)p.Wr + 1, &p.cc)) return -2;
+        p.gid = (const uint32_t *)v[0]; p.count = (const uint32_t *)v[1]; p.rounds = (const uint32_t *)v[2]; p.row = (const rg::I32x4 *)v[3];
+        p.log_list = (rg::U32x2 *)v[4]; p.commit_list = (rg::I32x4 *)v[5]; p.attention = (rg::U32x2 *)v[6]; p.counts = (uint32_t *)v[7];
+        HIP_TRY(t, rg::launch_effects(p, t->stream));
+        return 0;
+    }
+    // host memory: rows 0 .. n - 1 of rounds 0 .. R - 1 (and as much of the gid list) go in, n and R as two words; out come the counts and what the lists hold
+    const uint32_t n = !in->count ? C : (*in->count < C ? *in->count : C), R = !in->rounds ? D : (*in->rounds < 1 ? 1u : (*in->rounds < D ? *in->rounds : D));
+    for (uint32_t i = 0; in->gid && i < n; i++)
+        if (in->gid[i] >= t->G) return fail(t, -1, "%s: gid[%u] = %u, the table has %u groups", who, i, in->gid[i], t->G);
+    if (bind(t)) return -2;
+    hipStream_t s = t->stream;
+    Staging *fx = t->fx;
+    const uint32_t words[2] = {n, R};
+    if (stage_out(t, fx[E_LC], (size_t)p.Wc + 1, &p.lc) || stage_out(t, fx[E_AC], (size_t)p.Wc + 1, &p.ac) || stage_out(t, fx[E_CC], (size_t)p.Wr + 1, &p.cc) ||
+        stage_in(t, fx[E_WORDS], words, 2, s, &p.count) || (in->gid && stage_in(t, fx[E_GID], in->gid, (size_t)n, s, &p.gid)) || stage_out(t, fx[E_ROW], cells, &p.row) ||
+        (p.log_cap && stage_out(t, fx[E_LOG], (size_t)p.log_cap, &p.log_list)) || (p.commit_cap && stage_out(t, fx[E_COMMIT], (size_t)p.commit_cap, &p.commit_list)) ||
+        (p.attention_cap && stage_out(t, fx[E_ATTENTION], (size_t)p.attention_cap, &p.attention)) || stage_out(t, fx[E_COUNTS], 4, &p.counts))
+        return -2;
+    p.rounds = p.count + 1;
+    for (uint32_t r = 0; r < R; r++) HIP_TRY(t, col_up(fx[E_ROW], in->row, (size_t)r * C, n, s));
+    HIP_TRY(t, rg::launch_effects(p, s));
+    uint32_t counts[4] = {};
+    HIP_TRY(t, col_down(fx[E_COUNTS], counts, 0, 4, s));
+    HIP_TRY(t, hipStreamSynchronize(s));
+    memcpy(out->counts, counts, sizeof counts);
+    HIP_TRY(t, col_down(fx[E_LOG], out->log_list, 0, counts[0] < p.log_cap ? counts[0] : p.log_cap, s));          // entries beyond what was written are not touched
+    HIP_TRY(t, col_down(fx[E_COMMIT], out->commit_list, 0, counts[1] < p.commit_cap ? counts[1] : p.commit_cap, s));
+    HIP_TRY(t, col_down(fx[E_ATTENTION], out->attention, 0, counts[2] < p.attention_cap ? counts[2] : p.attention_cap, s));
     HIP_TRY(t, hipStreamSynchronize(s));
     return 0;
 }

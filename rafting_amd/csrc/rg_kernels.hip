@@ -910,9 +910,12 @@ hipError_t launch_tick_tail(const TickTailParams &p, int followers, hipStream_t 
 #define RG_ASSEMBLE_KERNELS 1
 #define RG_ROUTE_KERNELS 1
 #define RG_SCAN_KERNELS 1
+#define RG_EFFECTS_KERNELS 1
 #endif
 #include "rg_assemble.hpp"
 // ---- ... and their results back in arrival order (rg_route32)
 #include "rg_route.hpp"
 // ---- the table's groups by class (rg_scan) and a group's columns by a list of gids (rg_read_state_list / rg_load_state_list): load_group and the entry check of narrow_body above
 #include "rg_scan.hpp"
+// ---- what a launch asks a host to do, as lists (rg_effects32): timers_scan_kernel above
+#include "rg_effects.hpp"

@@ -31,7 +31,7 @@ def exported_symbols():
     """Every entry point include/raftgpu.h declares."""
     return [
         "rg_abi_version", "rg_table_create", "rg_table_destroy", "rg_last_error", "rg_table_groups",
-        "rg_table_cluster", "rg_table_option", "rg_load_state", "rg_read_state", "rg_submit", "rg_submit32", "rg_submit32c", "rg_submit32c_sparse", "rg_submit32c_sparse_rounds", "rg_outcome32_unpack", "rg_outcome32_unpack_rel", "rg_index_base_set", "rg_index_base_get", "rg_index_base_advance", "rg_index_base_advance32", "rg_batch32_pack_rel", "rg_batch32_pack", "rg_submit_async", "rg_submit_async_packed", "rg_submit_wait", "rg_tick_create", "rg_tick_launch", "rg_tick_wait", "rg_tick_destroy", "rg_tick2_create", "rg_tick2_create_sparse", "rg_tick2_create_sparse_rounds", "rg_tick2_launch", "rg_tick2_wait", "rg_tick2_destroy", "rg_assembler_create", "rg_assemble32", "rg_assembler_destroy", "rg_route32", "rg_assembler_carry_enable", "rg_assembler_carry_reset", "rg_assembler_carry_read", "rg_route32_carry", "rg_scan", "rg_read_state_list", "rg_load_state_list", "rg_timers_update32", "rg_health_update32", "rg_sync", "rg_step_kernel", "rg_host_alloc", "rg_host_free", "rg_dev_alloc",
+        "rg_table_cluster", "rg_table_option", "rg_load_state", "rg_read_state", "rg_submit", "rg_submit32", "rg_submit32c", "rg_submit32c_sparse", "rg_submit32c_sparse_rounds", "rg_outcome32_unpack", "rg_outcome32_unpack_rel", "rg_index_base_set", "rg_index_base_get", "rg_index_base_advance", "rg_index_base_advance32", "rg_batch32_pack_rel", "rg_batch32_pack", "rg_submit_async", "rg_submit_async_packed", "rg_submit_wait", "rg_tick_create", "rg_tick_launch", "rg_tick_wait", "rg_tick_destroy", "rg_tick2_create", "rg_tick2_create_sparse", "rg_tick2_create_sparse_rounds", "rg_tick2_launch", "rg_tick2_wait", "rg_tick2_destroy", "rg_assembler_create", "rg_assemble32", "rg_assembler_destroy", "rg_route32", "rg_assembler_carry_enable", "rg_assembler_carry_reset", "rg_assembler_carry_read", "rg_route32_carry", "rg_scan", "rg_read_state_list", "rg_load_state_list", "rg_effects32", "rg_timers_update32", "rg_health_update32", "rg_sync", "rg_step_kernel", "rg_host_alloc", "rg_host_free", "rg_dev_alloc",
         "rg_dev_free", "rg_copy_to_device", "rg_copy_to_host", "rg_stream", "rg_replicate", "rg_timers_configure", "rg_timers_update",
         "rg_timers_expired", "rg_timers_expired_epochs", "rg_timers_arm", "rg_timers_read", "rg_health_update", "rg_health_failure", "rg_ready", "rg_health_read", "rg_in_flight_read", "rg_in_flight_set",
         "rg_timing_enable",
@@ -142,6 +142,7 @@ def lib():
         L.rg_scan.argtypes = [vp, C.POINTER(abi.CScanQuery), C.POINTER(abi.CScanResult), i32]
         L.rg_read_state_list.argtypes = [vp, u32, vp, C.POINTER(abi.CGroupState)]
         L.rg_load_state_list.argtypes = [vp, u32, vp, C.POINTER(abi.CGroupState)]
+        L.rg_effects32.argtypes = [vp, C.POINTER(abi.CEffectsIn), C.POINTER(abi.CEffects), i32]
         L.rg_timers_update32.argtypes = [vp, u32, vp, vp, vp, i32]
         L.rg_health_update32.argtypes = [vp, u32, vp, vp, vp, i32]
         L.rg_replicate.argtypes = [vp, u32, vp, vp, vp, vp, vp, i32]
@@ -945,6 +946,39 @@ class Table:
     def scan_device(self, query, result):
         """one RG_MEM_DEVICE rg_scan on the table's stream: an abi.CScanQuery and an abi.CScanResult whose pointers are device-visible; asynchronous"""
         self._check(lib().rg_scan(self._h, C.byref(query), C.byref(result), abi.MEM_DEVICE))
+
+    # what a launch asks the host to do, as lists ------------------------------------------------------
+    def effects(self, row, capacity, max_rounds, gid=None, count=None, rounds=None, log_capacity=None, commit_capacity=None, attention_capacity=None, fill=0xAB):
+        """one synchronous RG_MEM_HOST run of rg_effects32 on numpy arrays (row [D * C] of abi.OUT32_DT; gid [C] or None: row i is group i; count / rounds: n and R,
+        None: C and D) -> SimpleNamespace(log_list, attention (abi.ROUTE_ITEM_DT), commit_list (abi.COMMIT_ITEM_DT), counts [4], the three capacities); every
+        output held `fill` bytes before the run. A capacity of None holds every possible item; a capacity of 0 comes with a NULL list."""
+        import types
+        Cc, D = int(capacity), int(max_rounds)
+        row = np.ascontiguousarray(row, dtype=abi.OUT32_DT)
+        gid = None if gid is None else np.ascontiguousarray(gid, dtype=np.uint32)
+        words = np.array([0 if count is None else count, 0 if rounds is None else rounds], np.uint32)
+        e = abi.CEffectsIn()
+        e.capacity, e.max_rounds, e.gid, e.row = Cc, D, abi._ptr(gid), row.ctypes.data
+        e.count, e.rounds = (None if count is None else words.ctypes.data), (None if rounds is None else words.ctypes.data + 4)
+
+        def blank(dt, k):
+            a = np.zeros(max(int(k), 1), dt)
+            a.view(np.uint8)[:] = fill
+            return a
+        cap = lambda c, most: int(most if c is None else c)      # noqa: E731
+        lcap, ccap, acap = cap(log_capacity, Cc * D), cap(commit_capacity, Cc), cap(attention_capacity, Cc * D)
+        out = types.SimpleNamespace(log_list=blank(abi.ROUTE_ITEM_DT, lcap), commit_list=blank(abi.COMMIT_ITEM_DT, ccap), attention=blank(abi.ROUTE_ITEM_DT, acap),
+                                    counts=blank(np.uint32, 4), log_capacity=lcap, commit_capacity=ccap, attention_capacity=acap)
+        o = abi.CEffects()
+        o.log_list, o.log_capacity = (out.log_list.ctypes.data if lcap else None), lcap
+        o.commit_list, o.commit_capacity = (out.commit_list.ctypes.data if ccap else None), ccap
+        o.attention, o.attention_capacity, o.counts = (out.attention.ctypes.data if acap else None), acap, out.counts.ctypes.data
+        self._check(lib().rg_effects32(self._h, C.byref(e), C.byref(o), abi.MEM_HOST))
+        return out
+
+    def effects_device(self, rows, lists):
+        """one RG_MEM_DEVICE rg_effects32 on the table's stream: an abi.CEffectsIn and an abi.CEffects whose pointers are device-visible; asynchronous"""
+        self._check(lib().rg_effects32(self._h, C.byref(rows), C.byref(lists), abi.MEM_DEVICE))
 
     # hot path ------------------------------------------------------------------------------------
     def submit(self, batch, out=None, fill=0):
